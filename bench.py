@@ -8,16 +8,22 @@ instance / image sequences already resident in HBM.  A "step" is one generated f
 the plan's input buffers (device-to-device) + one replay of the frame plan (per-lane segment hipGraphs on three streams).
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+A plain run sets up, warms up, times exactly --steps steps, writes the last timed step's outputs
+when --dump-outputs DIR is given, and prints ONE JSON line on rank 0 (metric, value, unit,
+ms_per_step, higher_is_better, dtype, ...).  --full adds every companion leg to that line:
   roofline     -- the dominant kernel (the implicit-GEMM conv template instance that carries the
                   1024->1024 3x3 ResnetBlock convolutions): algorithmic FLOP per launch / average
                   launch duration, durations measured with HIP events around every launch of an
                   eager replay of the same plan on the same stream (v2v_plan_profile);
   cpu_baseline -- the CPU oracle (port of the reference's algorithm, torch CPU ops) timed on this
-                  node's host cores on a bounded sample of the same workload (rank 0, N=1 only).
+                  node's host cores on a bounded sample of the same workload (rank 0, N=1 only);
+  and the parity checks against the CPU oracle, the fp32 / x3 / host-fed figures, the 2048x1024,
+  configs[0] / configs[3] and training companions (--mode train: the chunk parity, FlowNet2 alone
+  and the dominant weight-gradient kernel).
 """
 import argparse
 import json
@@ -183,6 +189,25 @@ def emit_record(full, stdout=None):
     stdout.flush()
 
 
+DUMP_LIMIT = 60 << 20      # bytes of all --dump-outputs arrays together (64 MB at most, .npy headers included)
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: name -> tensor, written as d/<name>.npy in float32.  Beyond DUMP_LIMIT in all, each array keeps its share
+    of the limit as a fixed sample (seeded flat indices, sorted), so that two runs of the same command stay comparable."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    outs = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in outs.values())
+    for k, a in outs.items():
+        if total > DUMP_LIMIT:
+            n = max(int(DUMP_LIMIT * (a.nbytes / total)) // a.itemsize, 1)
+            if n < a.size:
+                idx = np.sort(np.random.default_rng(0).integers(0, a.size, n))
+                a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, k + ".npy"), a)
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -213,8 +238,13 @@ def parse():
     ap.add_argument("--retune", action="store_true", help="ignore profiles/tune_cache.json and measure the tile selections in this run")
     ap.add_argument("--profile-frames", type=int, default=3)
     ap.add_argument("--no-train-line", action="store_true", help="infer: skip the short --mode train run reported under \"train\"")
-    ap.add_argument("--dump-ops", default="", help="write the per-op timing table (json) here")
-    ap.add_argument("--windows", type=int, default=5, help="timed windows of --steps frames each; `value` is the MEDIAN window")
+    ap.add_argument("--full", action="store_true", help="also run the companion legs (oracle parity, cpu_baseline, roofline, fp32 / x3 / "
+                    "host-fed figures, 2048x1024, configs[0] / [3], training; --mode train: chunk parity, FlowNet2, dominant kernel); "
+                    "off: the run does only what the headline figure needs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the arrays the last timed step returned "
+                    "(inference: fake_B, real_A_last; --mode train: fake_B, loss_G, loss_D) as DIR/<name>.npy in float32")
+    ap.add_argument("--dump-ops", default="", help="write the per-op timing table (json) here (with --full)")
+    ap.add_argument("--windows", type=int, default=1, help="timed windows of --steps frames each; `value` is the MEDIAN window")
     ap.add_argument("--min-warmup-s", type=float, default=0.5, help="warm up for at least this long (and at least --warmup frames) before the first window")
     ap.add_argument("--no-hires", action="store_true", help="infer: skip the 2048x1024 / 3-scale companion run reported under \"hires\"")
     ap.add_argument("--dry-run", action="store_true", help="plumbing check of the launch commands the driver uses (`--gpus N [--mode train]` under "
@@ -486,6 +516,8 @@ def run_train(args, dev, rank, world, local_rank, emit=True):
         for s in range(t_act):
             loss_backward(loss_D_T[s], optimizer_D_T[s])
         state["loss"] = (loss_G.detach(), loss_D.detach(), t_act)
+        if args.dump_outputs:
+            state["fake_B"] = fake_B.detach()
         state["i"] = i + n_frames_load if (i // n_frames_load + 1) < chunks_per_seq else 0
 
     # Round 6 (--train-graph): the chunk's whole launch sequence (G forward, FlowNet2, D / D_T, losses, the zero_grad / backward /
@@ -522,7 +554,7 @@ def run_train(args, dev, rank, world, local_rank, emit=True):
             torch.cuda.synchronize(dev)
 
     parity = None
-    if rank == 0 and world == 1 and not args.no_train_parity:
+    if args.full and rank == 0 and world == 1 and not args.no_train_parity:
         try:
             parity = train_parity(args, dev, local_rank, opt, modelG, modelD, flowNet)
         except Exception as ex:                                     # reported, never silently dropped
@@ -579,10 +611,12 @@ def run_train(args, dev, rank, world, local_rank, emit=True):
         elapsed = tt.item()
     fps = n_seqs * args.steps * n_frames_load / elapsed          # frames of all sequences (main() refuses world != --gpus)
     loss_G, loss_D, t_act = state["loss"]
+    if args.dump_outputs and rank == 0 and not dry:
+        dump_outputs(args.dump_outputs, {"fake_B": state["fake_B"], "loss_G": loss_G.reshape(1), "loss_D": loss_D.reshape(1)})
     finite = bool(torch.isfinite(loss_G).all().item() and torch.isfinite(loss_D).all().item())
     # FlowNet2 alone (frozen, inference: models/flownet2_pytorch via models/flownet.py:26-44): frame pairs per second
     flownet_line = None
-    if rank == 0 and not role_mode:
+    if args.full and rank == 0 and not role_mode:
         rb, rbp = B_all[:, 1:1 + n_frames_load], B_all[:, :n_frames_load]
         f0, c0 = flowNet.module.flops_launched, flowNet.module.convs_launched
         for _ in range(2):
@@ -606,7 +640,7 @@ def run_train(args, dev, rank, world, local_rank, emit=True):
     # (72 launches per 512x256 chunk, as many FLOP as the forward and backward-data launches of those layers), measured here with
     # HIP events on the stream it is launched on, alone on the chip, accumulating into .grad as in the step ----
     dominant = None
-    if rank == 0 and not dry and args.precision == "bf16" and not role_mode:
+    if args.full and rank == 0 and not dry and args.precision == "bf16" and not role_mode:
         try:
             dominant = train_dominant_kernel(dev, 8 * opt.ngf, H >> opt.n_downsample_G, W >> opt.n_downsample_G)
         except Exception as ex:
@@ -691,6 +725,10 @@ def run_train(args, dev, rank, world, local_rank, emit=True):
 def main():
     t_main = time.perf_counter()
     args = parse()
+    if args.dump_ops and not args.full:
+        raise SystemExit("bench.py: --dump-ops writes the per-op table of the roofline leg, which runs with --full only")
+    if args.dump_outputs and args.dry_run:
+        raise SystemExit("bench.py: --dump-outputs needs a device (a --dry-run executes nothing)")
     import torch
     import torch.distributed as dist
     if int(os.environ.get("V2V_ORACLE_THREADS", "0")) > 0:
@@ -797,6 +835,8 @@ def main():
             dist.barrier()
             torch.cuda.synchronize(dev)
 
+    last_out = {}                                # what the last timed step returned (--dump-outputs)
+
     def timed_fps(m, steps, warmup, windows=1, min_warm_s=0.0):
         """Warm up for >= `warmup` frames AND >= min_warm_s seconds (clocks ramp after the idle CPU legs), then time
         `windows` windows of EXACTLY `steps` frames, each bracketed by barrier + synchronize on both sides and reduced
@@ -813,7 +853,7 @@ def main():
             barrier()
             t0 = time.perf_counter()
             for _k in range(steps):
-                run_step(m, t)
+                last_out["v"] = run_step(m, t)
                 t += 1
             barrier()
             el = time.perf_counter() - t0
@@ -851,7 +891,7 @@ def main():
     # (a side figure, measured before the CPU oracle runs: after 128 oracle threads have been busy the launching thread of this
     # loop is measurably slower -- 258 instead of 300 frames/s -- although the GPU-resident `value` below is not affected)
     host_fed = None
-    if rank == 0 and world == 1 and not face:
+    if args.full and rank == 0 and world == 1 and not face:
         try:
             lab8, inst32 = lab.to(torch.uint8).cpu().pin_memory(), inst.to(torch.int32).cpu().pin_memory()
             # double-buffered staging: frame t+1's maps are uploaded on a copy stream while frame t's graph runs
@@ -907,7 +947,7 @@ def main():
     parity = None
     fp32_line = None
     x3_line = None
-    do_cpu = rank == 0 and args.gpus == 1 and not args.no_cpu_baseline
+    do_cpu = args.full and rank == 0 and args.gpus == 1 and not args.no_cpu_baseline
     if do_cpu:
         from oracle import vid2vid_oracle as O
         ncores = torch.get_num_threads()     # torch's default pool (one thread per physical core); SMT threads measured 9x slower
@@ -1038,6 +1078,9 @@ def main():
     # ---------------- the timed region ----------------
     elapsed, window_s, warm_frames = timed_fps(model, args.steps, args.warmup, args.windows, args.min_warmup_s)
     fps = world * args.steps / elapsed                           # world == --gpus (checked at start-up)
+    if args.dump_outputs and rank == 0:
+        fake_last, real_A_last = last_out["v"]
+        dump_outputs(args.dump_outputs, {"fake_B": fake_last, "real_A_last": real_A_last})
     fp = model._active_plan
     finite = bool(torch.isfinite(fp.out["fake_B"]).all().item())
 
@@ -1097,7 +1140,7 @@ def main():
         return "conv_igemm_kernel", "%dx%d,splitK=%d" % (bm, bn, dom[1])
 
     roofline = None
-    if rank == 0:
+    if args.full and rank == 0:
         nprof = max(args.profile_frames, 1)
         acc, rows, convs, launches, mfma_log, total_ms = kernel_table(fp, nprof)
         dom = max(acc, key=lambda k: acc[k]["flops"])
@@ -1507,8 +1550,8 @@ def main():
             "dtype": args.precision, "data": "synthetic",
             "timing": {"windows_ms_per_step": [round(e / args.steps * 1e3, 4) for e in window_s], "statistic": "median window",
                        "warmup_frames_run": warm_frames, "min_warmup_s": args.min_warmup_s,
-                       "note": "%d windows of exactly --steps frames, each bracketed by barrier + synchronize and MAX-reduced over ranks; "
-                               "`value` / `ms_per_step` are the median window" % len(window_s)},
+                       "note": "%d window%s of exactly --steps frames, each bracketed by barrier + synchronize and MAX-reduced over ranks; "
+                               "`value` / `ms_per_step` are the median window" % (len(window_s), "" if len(window_s) == 1 else "s")},
             "config": {"workload": "%s %dx%d inference, n_scales_spatial=%d, %s, ngf=128 n_blocks=9 "
                                    "(%.1fM params random-init, %.0f GFLOP/frame as dense convolutions%s), batch 1 per sequence, 1 sequence per GPU"
                                    % (args.dataset, W, H, args.scales, "input_nc=15, no fg tower" if face else "--fg --use_instance", sum(q.numel() for q in model.parameters()) / 1e6,
@@ -1532,7 +1575,7 @@ def main():
             "cpu_baseline": cpu,
         }
         # ---- companion figure: the OTHER resolution of BASELINE's metric, 2048x1024 with n_scales_spatial=3 (configs[4] geometry) ----
-        if world == 1 and not args.no_hires and not face and args.scales == 1 and (W, H) == (512, 256):
+        if args.full and world == 1 and not args.no_hires and not face and args.scales == 1 and (W, H) == (512, 256):
             sys.stdout = sys.stderr
             try:
                 model = fp = None
@@ -1584,6 +1627,7 @@ def main():
                 torch.cuda.empty_cache()
                 targs = argparse.Namespace(**vars(args))
                 targs.mode, targs.steps, targs.warmup, targs.no_vgg = "train", 6, 2, False
+                targs.dump_outputs = ""                 # --dump-outputs holds the headline's last frame
                 for k_, v_ in over.items():
                     setattr(targs, k_, v_)
                 _t = time.perf_counter()
@@ -1604,19 +1648,19 @@ def main():
                 out[key] = {"error": repr(ex)[:300]}
             finally:
                 sys.stdout = _stdout
-        if world == 1 and not args.no_train_line and not face and args.scales == 1:
+        if args.full and world == 1 and not args.no_train_line and not face and args.scales == 1:
             model = None
             train_companion("train")
         # ---- BASELINE configs[4] geometry as a TRAINING chunk on one GPU: 2048x1024, n_scales_spatial=3, num_D=4 + VGG as
         # scripts/street/train_2048.sh, n_frames_total=6, one frame per chunk (each generator GPU's share of the n_gpus_gen split),
         # all scales trained; fp32 chunk-vs-oracle parity (outputs, every loss, complete G / D gradients) before timing ----
-        if world == 1 and not args.no_train_hires and not face and args.scales == 1 and (W, H) == (512, 256):
+        if args.full and world == 1 and not args.no_train_hires and not face and args.scales == 1 and (W, H) == (512, 256):
             model = None
             train_companion("train_hires", width=2048, height=1024, scales=3, num_D=4, frames_total=6, frames_per_gpu=1,
                             no_train_parity=bool(not args.train_hires_parity or args.no_cpu_baseline), no_bf16_train_parity=True)
         # ---- BASELINE configs[2] geometry as a training chunk on one GPU (1024x512, n_scales_spatial=2, num_D=3): frames trained/s only --
         # its fp32 chunk-vs-oracle parity is tests/test_gpu_golden.py::test_full_width_training_chunk_1024x512_s2_vs_oracle ----
-        if world == 1 and not args.no_train_c3 and not face and args.scales == 1 and (W, H) == (512, 256):
+        if args.full and world == 1 and not args.no_train_c3 and not face and args.scales == 1 and (W, H) == (512, 256):
             model = None
             train_companion("train_c3", width=1024, height=512, scales=2, num_D=3, frames_total=6, frames_per_gpu=2, no_train_parity=True)
         # ---- flat scalars ahead of the nested objects: the figures that carry north_star's 1e-3 parity and the second resolution ----

@@ -1,5 +1,5 @@
 cd $GRAFT_REPO_ROOT
-LEAN="--no-cpu-baseline --no-train-line --no-train-hires --no-c1 --no-c4 --no-train-c3"
+LEAN="--full --no-cpu-baseline --no-train-line --no-train-hires --no-c1 --no-c4 --no-train-c3"
 for rep in 1 2; do
 for v in 0 1; do
 V2V_RAW_BF16=$v timeout 900 python bench.py $LEAN 2>gpurun_out/rawall_$v.err | python -c "

@@ -181,3 +181,24 @@ def test_emit_record_writes_one_line_and_the_full_record(line, tmp_path, monkeyp
     assert json.loads(lines[0])["full_record"] == bench.FULL_RECORD
     full = json.load(open(tmp_path / bench.FULL_RECORD))
     assert full["value"] == line["value"] and "train" in full and len(err.getvalue()) < 200
+
+
+def test_dump_outputs_are_float32_bounded_and_repeatable(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array as <name>.npy in float32; beyond the byte limit each array keeps its share as the same
+    seeded sample in every run, so that two builds can be compared output for output."""
+    import numpy as np
+    import torch
+    import bench
+    bench.dump_outputs(str(tmp_path / "small"), {"fake_B": torch.arange(6, dtype=torch.bfloat16).view(1, 2, 3)})
+    a = np.load(tmp_path / "small" / "fake_B.npy")
+    assert a.dtype == np.float32 and a.shape == (1, 2, 3) and a.ravel().tolist() == list(range(6))
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 4000)
+    g = torch.Generator().manual_seed(1)
+    arrays = {"big": torch.randn(3000, generator=g), "small": torch.randn(100, generator=g)}
+    for run in ("r1", "r2"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    out = {run: {n: np.load(tmp_path / run / (n + ".npy")) for n in arrays} for run in ("r1", "r2")}
+    assert sum(v.nbytes for v in out["r1"].values()) <= 4000
+    assert all(v.dtype == np.float32 for v in out["r1"].values())
+    assert all(np.array_equal(out["r1"][n], out["r2"][n]) for n in arrays)
+    assert set(out["r1"]["big"].tolist()) <= set(arrays["big"].tolist())
