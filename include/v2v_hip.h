@@ -400,6 +400,30 @@ int v2v_pack_concat_nhwc(const float* x0, int32_t C0, const float* x1, int32_t C
 /* channels [c_offset, c_offset+C) of an NHWC tensor -> planar fp32 NCHW (backward of the above) */
 int v2v_unpack_channels_nchw(const void* y, float* x, int32_t N, int32_t C, int32_t H, int32_t W,
                              int32_t c_stride, int32_t c_offset, int32_t dtype, void* stream);
+/* Face discriminator window (--add_face_disc; reference models/vid2vid_model_D.py:38-40 netD_f, :149-160 forward, :215-230
+ * get_face_region).  real_A planar fp32 [N][C][H][W] (C >= 3).  The face mask is real_A[:,2] > 0.9 (V2V_FACE_DENSEPOSE) or,
+ * with --openpose_only, (c0 > 0.19) & (c0 < 0.21) & (c1 < -0.99) & (c2 > -0.61) & (c2 < -0.59) (V2V_FACE_OPENPOSE), compared in
+ * fp32.  One box over all N frames; from its inclusive bounds yc = (ys+ye)//2, clamped to [crop_h/2, H-1-crop_h/2], window
+ * [yc-crop_h/2, yc+crop_h/2), the same for x (crop_h = crop_w = fineSize//32*8 in the reference).  Writes the caller-owned
+ * device int32[8] `win` = {found, ys, ye, xs, xe, 0, 0, 0}; with no face pixel found = 0 and the window is the in-bounds
+ * top-left one.  Every call resets its accumulators in its own launches (reset, reduce, finalize on `stream`): nothing of an
+ * earlier call is read.  crop_h, crop_w even, 0 < crop <= H, W; otherwise V2V_EINVAL. */
+#define V2V_FACE_DENSEPOSE 0
+#define V2V_FACE_OPENPOSE  1
+#define V2V_FACE_WIN_WORDS 8
+int v2v_face_window(const float* real_A, int32_t N, int32_t C, int32_t H, int32_t W, int32_t mode,
+                    int32_t crop_h, int32_t crop_w, int32_t* win, void* stream);
+/* v2v_pack_concat_nhwc (scale1 = 1) of the window: cat([x0, x1], 1)[:, :, ys:ys+crop_h, xs:xs+crop_w] -> NHWC
+ * [N][crop_h][crop_w][c_stride] in `dtype`, the window origin read from `win` (v2v_face_window) on the device
+ * (reference :153-154, real_A[win] / real_B[win] / fake_B[win]). */
+int v2v_pack_concat_window_nhwc(const float* x0, int32_t C0, const float* x1, int32_t C1, int32_t N, int32_t H, int32_t W,
+                                const int32_t* win, int32_t crop_h, int32_t crop_w, void* y, int32_t c_stride,
+                                int32_t dtype, void* stream);
+/* backward of the x1 operand of the above: channels [c_offset, c_offset+C) of dy [N][crop_h][crop_w][c_stride] -> the full
+ * planar fp32 gradient dx [N][C][H][W]: the window's values inside it, zeros outside (one pass, no memset). */
+int v2v_unpack_window_nchw(const void* dy, const int32_t* win, int32_t N, int32_t C, int32_t H, int32_t W,
+                           int32_t crop_h, int32_t crop_w, int32_t c_stride, int32_t c_offset, float* dx,
+                           int32_t dtype, void* stream);
 /* backward of nn.ReflectionPad2d(pad): xp [N][H+2p][W+2p][cs] -> x [N][H][W][cs] */
 int v2v_reflect_pad_fold(const void* xp, void* x, int32_t N, int32_t H, int32_t W, int32_t pad,
                          int32_t c_stride, int32_t dtype, void* stream);

@@ -295,6 +295,48 @@ def pack_concat(eng, x0, x1=None, scale1=1.0):
     return Act(PackFn.apply(eng, x0, x1, scale1), c)
 
 
+class PackWindowFn(torch.autograd.Function):
+    """cat([x0, x1], 1)[:, :, ys:ye, xs:xe] of planar fp32 NCHW -> NHWC engine dtype, the window read on the device from an
+    int32 {found, ys, ye, xs, xe} buffer (Engine.face_window): the face discriminator's input (reference
+    models/vid2vid_model_D.py:153-154).  Differentiable w.r.t. x1 only."""
+
+    @staticmethod
+    def forward(ctx, eng, x0, x1, win, crop_h, crop_w):
+        x0 = x0.contiguous().float()
+        x1 = x1.contiguous().float()
+        N, C0, H, W = x0.shape
+        C1 = x1.shape[1]
+        if ctx.needs_input_grad[1]:
+            raise NotImplementedError("pack_concat_window: the first operand (real_A) is never differentiated on this path")
+        cs = pad_channels(C0 + C1, eng.dtype)
+        y = torch.empty((N, crop_h, crop_w, cs), dtype=eng.tdtype, device=eng.device)
+        check(lib.v2v_pack_concat_window_nhwc(_ptr(x0), C0, _ptr(x1), C1, N, H, W, _ptr(win), crop_h, crop_w, _ptr(y), cs,
+                                              eng.dtype, _stream()), "pack_concat_window")
+        ctx.eng, ctx.dims = eng, (N, C0, C1, H, W, crop_h, crop_w, cs)
+        ctx.save_for_backward(win)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        eng = ctx.eng
+        N, C0, C1, H, W, crop_h, crop_w, cs = ctx.dims
+        (win,) = ctx.saved_tensors
+        d1 = None
+        if ctx.needs_input_grad[2]:
+            dy = dy.contiguous()
+            d1 = torch.empty((N, C1, H, W), dtype=torch.float32, device=eng.device)
+            check(lib.v2v_unpack_window_nchw(_ptr(dy), _ptr(win), N, C1, H, W, crop_h, crop_w, cs, C0, _ptr(d1), eng.dtype,
+                                             _stream()), "unpack_window")
+        return None, None, d1, None, None, None
+
+
+def pack_concat_window(eng, x0, x1, win, crop):
+    """Act of cat([x0, x1], dim=1) cropped to the (crop_h, crop_w) window whose origin the device buffer `win` holds;
+    differentiable w.r.t. x1."""
+    crop_h, crop_w = crop
+    return Act(PackWindowFn.apply(eng, x0, x1, win, int(crop_h), int(crop_w)), x0.shape[1] + x1.shape[1])
+
+
 class UnpackFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, eng, y, Cc):

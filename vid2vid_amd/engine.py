@@ -756,6 +756,18 @@ class Engine:
             torch.cuda.current_stream(self.device).wait_stream(side)
         torch.autograd.Variable._execution_engine.queue_callback(join)
 
+    def face_window(self, real_A, openpose, crop_h, crop_w, name="face_win"):
+        """v2v_face_window of planar fp32 real_A (N, C, H, W) into this engine's int32[8] buffer `name`:
+        {found, ys, ye, xs, xe} of Vid2VidModelD.get_face_region (reference models/vid2vid_model_D.py:215-230), on the
+        device -- no host read, no allocation after the first call.  The buffer is rewritten by the next call with the
+        same name; the window packs of a discriminator pass (autograd.pack_concat_window) read it in their backward."""
+        real_A = real_A.contiguous().float()
+        N, Cc, H, W = real_A.shape
+        win = self.scratch(name, L.FACE_WIN_WORDS, dtype=torch.int32, zero=True)
+        mode = L.FACE_OPENPOSE if openpose else L.FACE_DENSEPOSE
+        check(lib.v2v_face_window(_ptr(real_A), N, Cc, H, W, mode, crop_h, crop_w, _ptr(win), _stream()), "face_window")
+        return win
+
     def zero_page(self):
         """256 zero bytes: source of padded / ragged lanes of the LDS-DMA loaders."""
         if self._zero_page is None:

@@ -66,6 +66,8 @@ class WgradDesc(C.Structure):
 
 
 LOSS_MSE_CONST, LOSS_L1 = 0, 1
+FACE_DENSEPOSE, FACE_OPENPOSE = 0, 1
+FACE_WIN_WORDS = 8
 
 # name -> (restype, argtypes); mirrors include/v2v_hip.h one to one
 _P, _I, _L, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -89,6 +91,9 @@ PROTOTYPES = {
     "v2v_avgpool3s2_nhwc_backward": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "v2v_pack_concat_nhwc": (C.c_int, [_P, _I, _P, _I, _F, _P, _I, _I, _I, _I, _I, _P]),
     "v2v_unpack_channels_nchw": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "v2v_face_window": (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "v2v_pack_concat_window_nhwc": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P]),
+    "v2v_unpack_window_nchw": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "v2v_reflect_pad_fold": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "v2v_warp_blend_backward": (C.c_int, [_P] * 15 + [_I] * 5 + [_P]),
     "v2v_resample_flow_backward": (C.c_int, [_P] * 7 + [_I] * 5 + [_P]),

@@ -6,6 +6,18 @@ API-compatible with the reference's models/vid2vid_model_D.py: `initialize(opt)`
 `optimizer_D_T{s}`.  Every discriminator forward, loss reduction and their backward passes are
 libv2v_hip.so launches recorded as `v2v` custom ops (autograd.py); the only torch arithmetic left is
 the addition / scaling of the (1,1) loss scalars, exactly where the reference has it.
+
+--add_face_disc (the pose2body recipes; reference :38-40, :149-160, :215-230) adds the face discriminator netD_f on a
+fixed-size crop around the face.  The crop's position depends on the label map, so it is computed on the device
+(v2v_face_window, Engine.face_window) and read by the window packs on the device: forward needs no device-to-host read and
+the three netD_f passes always run on the static crop shape.  The reference skips the face terms when the mask is empty;
+here the four face losses are multiplied by the device-side `found` flag, a float (1,1) tensor, instead.  Consequences:
+  * with no face, the four face losses, every netD_f gradient and the face path's fake_B gradient are exact zeros;
+  * netD_f's Adam moments still advance on such a step (FusedAdam steps every parameter of its flat buffer, the convention
+    it already has for every parameter), and so do netD_f's BatchNorm running statistics (vid2vid never reads them: its
+    norms always run in training mode).
+`get_face_region(real_A)` is the reference's public method (util.save_all_tensors calls it on display steps): the same
+kernel, then a host read of the five words.
 """
 import torch
 
@@ -24,8 +36,6 @@ class Vid2VidModelD(BaseModel):
         self.tD = opt.n_frames_D
         self.output_nc = opt.output_nc
         self.n_scales = opt.n_scales_spatial
-        if opt.add_face_disc:
-            raise NotImplementedError("--add_face_disc (pose recipes) is outside the MI355X hot path (SURVEY 8a13)")
         if not opt.no_vgg:          # reference :66-67; the weights are torchvision's download -> a path option here
             self.criterionVGG = networks.VGGLoss(self.device.index if self.device.type == "cuda" else -1,
                                                  getattr(opt, "vgg19_checkpoint", "checkpoints/vgg19-dcbb9e9d.pth"),
@@ -41,6 +51,9 @@ class Vid2VidModelD(BaseModel):
         gpu_ids = self.dev_ids
         self.netD = networks.define_D(netD_input_nc, opt.ndf, opt.n_layers_D, opt.norm, opt.num_D,
                                       not opt.no_ganFeat, gpu_ids=gpu_ids)
+        if opt.add_face_disc:       # face discriminator (reference :38-40): netD's input width, num_D - 2 scales (>= 1)
+            self.netD_f = networks.define_D(netD_input_nc, opt.ndf, opt.n_layers_D, opt.norm, max(1, opt.num_D - 2),
+                                            not opt.no_ganFeat, gpu_ids=gpu_ids)
         # temporal discriminators (reference :42-46)
         netD_input_nc = opt.output_nc * opt.n_frames_D + 2 * (opt.n_frames_D - 1)
         for s in range(opt.n_scales_temporal):
@@ -53,16 +66,23 @@ class Vid2VidModelD(BaseModel):
             self.load_network(self.netD, "D", opt.which_epoch, opt.load_pretrain)
             for s in range(opt.n_scales_temporal):
                 self.load_network(getattr(self, "netD_T" + str(s)), "D_T" + str(s), opt.which_epoch, opt.load_pretrain)
+            if opt.add_face_disc:   # (reference :56-57; a checkpoint without D_f -- the 512p recipe's 256p one -- is tolerated)
+                self.load_network(self.netD_f, "D_f", opt.which_epoch, opt.load_pretrain)
 
         self.old_lr = opt.lr
         self.loss_names = ["G_VGG", "G_GAN", "G_GAN_Feat", "D_real", "D_fake", "G_Warp", "F_Flow", "F_Warp", "W"]
         self.loss_names_T = ["G_T_GAN", "G_T_GAN_Feat", "D_T_real", "D_T_fake", "G_T_Warp"]
+        if opt.add_face_disc:
+            self.loss_names += ["G_f_GAN", "G_f_GAN_Feat", "D_f_real", "D_f_fake"]
 
         if opt.TTUR:
             beta1, beta2, lr = 0, 0.9, opt.lr * 2
         else:
             beta1, beta2, lr = opt.beta1, 0.999, opt.lr
-        self.optimizer_D = FusedAdam(list(self.netD.parameters()), lr=lr, betas=(beta1, beta2))
+        params = list(self.netD.parameters())
+        if opt.add_face_disc:       # (reference :73-79: netD's parameters, then netD_f's)
+            params += list(self.netD_f.parameters())
+        self.optimizer_D = FusedAdam(params, lr=lr, betas=(beta1, beta2))
         for s in range(opt.n_scales_temporal):
             params = list(getattr(self, "netD_T" + str(s)).parameters())
             setattr(self, "optimizer_D_T" + str(s), FusedAdam(params, lr=opt.lr, betas=(opt.beta1, 0.999)))
@@ -95,17 +115,19 @@ class Vid2VidModelD(BaseModel):
                     loss_FM = loss_FM + AG.l1_act(eng, pred_fake[i][j], pred_real[i][j], weight=w)
         return loss_G_GAN, loss_FM
 
-    def _run_D(self, netD, x0, x1, scale1=1.0, tag="D"):
+    def _run_D(self, netD, x0, x1, scale1=1.0, tag="D", window=None):
         eng = self.engine
+        if window is not None:      # (win, (crop_h, crop_w)): the face crop, positioned on the device
+            return netD.emit(eng, AG.pack_concat_window(eng, x0, x1, window[0], window[1]), tag=tag)
         return netD.emit(eng, AG.pack_concat(eng, x0, x1, scale1), tag=tag)
 
-    def compute_loss_D(self, netD, real_A, real_B, fake_B):
-        """reference :168-179 -- three discriminator passes (real, fake detached, fake)."""
-        pred_real = self._run_D(netD, real_A, real_B)
-        pred_fake = self._run_D(netD, real_A, fake_B.detach())
+    def compute_loss_D(self, netD, real_A, real_B, fake_B, window=None, tag="D"):
+        """reference :168-179 -- three discriminator passes (real, fake detached, fake); `window`: on the face crop."""
+        pred_real = self._run_D(netD, real_A, real_B, tag=tag, window=window)
+        pred_fake = self._run_D(netD, real_A, fake_B.detach(), tag=tag, window=window)
         loss_D_real = self.criterionGAN(pred_real, True)
         loss_D_fake = self.criterionGAN(pred_fake, False)
-        pred_fake = self._run_D(netD, real_A, fake_B)
+        pred_fake = self._run_D(netD, real_A, fake_B, tag=tag, window=window)
         loss_G_GAN, loss_G_GAN_Feat = self.GAN_and_FM_loss(pred_real, pred_fake)
         return loss_D_real, loss_D_fake, loss_G_GAN, loss_G_GAN_Feat
 
@@ -180,7 +202,42 @@ class Vid2VidModelD(BaseModel):
 
         loss_list = [loss_G_VGG, loss_G_GAN, loss_G_GAN_Feat, loss_D_real, loss_D_fake,
                      loss_G_Warp, loss_F_Flow, loss_F_Warp, loss_W]
+        if getattr(opt, "add_face_disc", False):       # (reference :149-160)
+            loss_list += self._face_losses(real_A, real_B, fake_B)
         return [l.view(-1, 1) for l in loss_list]
+
+    # ------------------------------------------------------------------ face discriminator (--add_face_disc)
+    def _face_crop(self, H, W):
+        """(ylen, xlen) of get_face_region: fineSize // 32 * 8 (reference :224-225)."""
+        crop = self.opt.fineSize // 32 * 8
+        if crop > H or crop > W:
+            raise ValueError("--add_face_disc: the face crop (fineSize // 32 * 8 = %d) does not fit the %dx%d frame; "
+                             "the reference shrinks the crop silently there, this backend does not" % (crop, W, H))
+        return crop, crop
+
+    def _face_losses(self, real_A, real_B, fake_B):
+        """[G_f_GAN, G_f_GAN_Feat, D_f_real, D_f_fake] of reference :149-160 with the window kept on the device: the three
+        netD_f passes run on the crop the window buffer positions, and the losses are multiplied by its `found` word."""
+        eng = self.engine
+        _, _, H, W = real_A.shape
+        crop = self._face_crop(H, W)
+        win = eng.face_window(real_A, self.opt.openpose_only, crop[0], crop[1])
+        found = win[:1].view(1, 1).float()
+        l_real, l_fake, l_gan, l_feat = self.compute_loss_D(self.netD_f, real_A, real_B, fake_B, window=(win, crop), tag="D_f")
+        face_weight = 2
+        return [l_gan * face_weight * found, l_feat * face_weight * found, l_real * found, l_fake * found]
+
+    def get_face_region(self, real_A):
+        """reference :215-230: (ys, ye, xs, xe) as Python ints of the fixed-size window around the face pixels of all frames
+        of real_A (N, C, H, W), or four None without a face pixel.  Reads the device result back (display path only)."""
+        real_A = real_A.to(self.device, torch.float32)
+        _, _, H, W = real_A.shape
+        crop = self._face_crop(H, W)
+        win = self.engine.face_window(real_A, self.opt.openpose_only, crop[0], crop[1], name="face_win_query")
+        found, ys, ye, xs, xe = [int(v) for v in win[:5].tolist()]
+        if not found:
+            return None, None, None, None
+        return ys, ye, xs, xe
 
     # ------------------------------------------------------------------ bookkeeping used by train.py
     def get_all_skipped_frames(self, frames_all, real_B, fake_B, flow_ref, conf_ref, t_scales, tD, n_frames_load, i, flowNet):
@@ -205,6 +262,9 @@ class Vid2VidModelD(BaseModel):
         loss_D = (loss_dict["D_fake"] + loss_dict["D_real"]) * 0.5
         loss_G = loss_dict["G_GAN"] + loss_dict["G_GAN_Feat"] + loss_dict["G_VGG"]
         loss_G = loss_G + loss_dict["G_Warp"] + loss_dict["F_Flow"] + loss_dict["F_Warp"] + loss_dict["W"]
+        if getattr(self.opt, "add_face_disc", False):
+            loss_G = loss_G + loss_dict["G_f_GAN"] + loss_dict["G_f_GAN_Feat"]
+            loss_D = loss_D + (loss_dict["D_f_fake"] + loss_dict["D_f_real"]) * 0.5
         loss_D_T = []
         t_scales_act = min(t_scales, len(loss_dict_T))
         for s in range(t_scales_act):
@@ -216,6 +276,8 @@ class Vid2VidModelD(BaseModel):
         self.save_network(self.netD, "D", label, self.gpu_ids)
         for s in range(self.opt.n_scales_temporal):
             self.save_network(getattr(self, "netD_T" + str(s)), "D_T" + str(s), label, self.gpu_ids)
+        if getattr(self.opt, "add_face_disc", False):
+            self.save_network(self.netD_f, "D_f", label, self.gpu_ids)
 
 
 # --------------------------------------------------------------------------------------

@@ -397,7 +397,8 @@ def wrap_roles(opt, modelG, modelD, flowNet, layout):
         if L.pg_D is not None:
             gsd.broadcast(modelD.optimizer_D.flat.flat_param, src=L.n_gen + 0)
             if hasattr(modelD, "netD"):
-                _broadcast_state([modelD.netD], L.pg_D, L.n_gen + 0)
+                # netD_f (--add_face_disc) lives with netD on D-rank 0; its parameters are in optimizer_D's flat buffer too
+                _broadcast_state([modelD.netD] + ([modelD.netD_f] if hasattr(modelD, "netD_f") else []), L.pg_D, L.n_gen + 0)
     else:
         modelD.optimizer_D = NullOptimizer(lr)
     for s in range(t_scales):
@@ -420,6 +421,8 @@ def wrap_roles(opt, modelG, modelD, flowNet, layout):
     def save_d(label):
         if L.owns_D and L.saves:
             save_net(modelD.netD, "D", label, modelD.gpu_ids)
+            if hasattr(modelD, "netD_f"):
+                save_net(modelD.netD_f, "D_f", label, modelD.gpu_ids)
         if L.owns_DT and L.saves:
             for s in range(t_scales):
                 save_net(getattr(modelD, "netD_T" + str(s)), "D_T" + str(s), label, modelD.gpu_ids)
