@@ -25,6 +25,9 @@
  *   v2v_correlation_forward   correlation_cuda.forward  (correlation_cuda.cc:10-87)
  *   v2v_resample2d_forward    resample2d_cuda.forward   (resample2d_cuda.cc:6-13)
  *   v2v_channelnorm_forward   channelnorm_cuda.forward  (channelnorm_cuda.cc:6-14)
+ *   v2v_correlation_backward  correlation_cuda.backward (correlation_cuda.cc:89-167)
+ *   v2v_resample2d_backward   resample2d_cuda.backward  (resample2d_cuda.cc:15-26)
+ *   v2v_channelnorm_backward  channelnorm_cuda.backward (channelnorm_cuda.cc:16-25)
  */
 #ifndef V2V_HIP_H
 #define V2V_HIP_H
@@ -470,6 +473,17 @@ int v2v_correlation_forward(const float* in1, const float* in2, float* out,
                             int32_t N, int32_t C, int32_t H, int32_t W,
                             int32_t pad_size, int32_t kernel_size, int32_t max_displacement,
                             int32_t stride1, int32_t stride2, int32_t corr_type_multiply, void* stream);
+/* correlation_cuda.backward (correlation_cuda.cc:89-167, kernels correlation_cuda_kernel.cu:150-241 and :243-334): the exact adjoint
+ * of v2v_correlation_forward.  grad_out: [N][out_c][out_h][out_w], which must be the extent v2v_correlation_out_size gives
+ * (otherwise V2V_EINVAL); grad_in1 / grad_in2: [N][C][H][W], each written completely (no pre-zeroing, no rInput / rbot scratch);
+ * one of the two may be NULL, that gradient is then not computed.  Gather form: every element is summed by one lane in a fixed
+ * order, no atomics -- the result is bit-identical from run to run.  Arguments the forward entry rejects are rejected here
+ * with the same code.  FlowNetC's geometry class (FlowNetC.py:31) takes an LDS-staged tile kernel, every other parameter set a
+ * simple one. */
+int v2v_correlation_backward(const float* in1, const float* in2, const float* grad_out, float* grad_in1, float* grad_in2,
+                             int32_t N, int32_t C, int32_t H, int32_t W, int32_t out_c, int32_t out_h, int32_t out_w,
+                             int32_t pad_size, int32_t kernel_size, int32_t max_displacement,
+                             int32_t stride1, int32_t stride2, int32_t corr_type_multiply, void* stream);
 /* The same correlation for FlowNetC's geometry class (kernel_size 1, stride1 1, stride2 2, pad = max_displacement: FlowNetC.py:31)
  * on the matrix pipe, between two NHWC activation tensors [N][H][W][cs_in] (C real channels, dtype = activation dtype), fused with
  * what surrounds it in FlowNetC.forward (FlowNetC.py:86-93): the result / C passes LeakyReLU(leaky_slope) and lands as
@@ -482,9 +496,23 @@ int v2v_correlation_nhwc(const void* f1, const void* f2, void* out, int32_t N, i
 int v2v_resample2d_forward(const float* img, const float* flow, float* out,
                            int32_t N, int32_t C, int32_t H, int32_t W, int32_t OH, int32_t OW,
                            int32_t kernel_size, void* stream);
+/* resample2d_cuda.backward (resample2d_cuda.cc:15-26, kernels resample2d_kernel.cu:67-117 and :119-190).  grad_out: [N][C][OH][OW];
+ * grad_img: [N][C][H][W], grad_flow: [N][2][OH][OW]; one of the two may be NULL (not computed).  Same arithmetic as the
+ * reference: indices clamped, weights from the unclamped fractional part, the reference's expression for d/dflow.  grad_img is a
+ * scatter with float atomics like the reference's: it is zeroed inside the call, and its summation ORDER is run-dependent
+ * (differences at the 1e-7 level).  grad_flow is a gather over the channels: deterministic.  kernel_size > 1: indices are clamped
+ * to the output extent and all kernel_size^2 taps are differentiated, as the forward pass computes them. */
+int v2v_resample2d_backward(const float* img, const float* flow, const float* grad_out, float* grad_img, float* grad_flow,
+                            int32_t N, int32_t C, int32_t H, int32_t W, int32_t OH, int32_t OW,
+                            int32_t kernel_size, void* stream);
 /* channelnorm_cuda.forward (channelnorm_kernel.cu:18-60): out[b,0,y,x] = sqrt(sum_c x^2) */
 int v2v_channelnorm_forward(const float* x, float* out, int32_t N, int32_t C, int32_t H, int32_t W,
                             int32_t norm_deg, void* stream);
+/* channelnorm_cuda.backward (channelnorm_cuda.cc:16-25, kernel channelnorm_kernel.cu:63-96):
+ * grad_in[b,c,y,x] = grad_out[b,0,y,x] * x[b,c,y,x] / (out[b,0,y,x] + 1e-9), `out` being the forward result.  norm_deg 2 only,
+ * like the forward entry. */
+int v2v_channelnorm_backward(const float* x, const float* out, const float* grad_out, float* grad_in,
+                             int32_t N, int32_t C, int32_t H, int32_t W, int32_t norm_deg, void* stream);
 
 /* ---- FlowNet2 glue (models/flownet2_pytorch/models.py:96-161, models/flownet.py:43-59) ---- */
 /* x1, x2 [B][3][HW] = (im1, im2 - rgb_mean) / rgb_max, rgb_mean per (b, c) over both frames (models.py:97-102).

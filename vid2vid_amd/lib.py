@@ -146,6 +146,9 @@ PROTOTYPES = {
     "v2v_correlation_nhwc": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _P]),
     "v2v_resample2d_forward": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "v2v_channelnorm_forward": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "v2v_correlation_backward": (C.c_int, [_P] * 5 + [_I] * 13 + [_P]),
+    "v2v_resample2d_backward": (C.c_int, [_P] * 5 + [_I] * 7 + [_P]),
+    "v2v_channelnorm_backward": (C.c_int, [_P] * 4 + [_I] * 5 + [_P]),
     "v2v_plan_create": (_P, []),
     "v2v_plan_destroy": (None, [_P]),
     "v2v_plan_begin_record": (C.c_int, [_P]),
