@@ -314,6 +314,42 @@ int v2v_act_backward(const void* dy, const void* y, void* g, int32_t N, int32_t 
                      int32_t c_stride_in, int32_t c_stride_out, int32_t nchw, int32_t act, float act_param,
                      float out_scale, int32_t dtype, void* stream);
 
+/* ---- InstanceNorm2d at any batch size (csrc/instance_norm.hip) ----
+ * get_norm_layer('instance') = functools.partial(nn.InstanceNorm2d, affine=False) (models/networks.py:23-30) in training
+ * mode (.eval() is never called): statistics per SAMPLE and channel over the sample's HW = OH*OW pixels, biased variance,
+ * exactly torch.nn.functional.instance_norm(x, eps=eps).  Running statistics are not tracked (the reference's norm has none).
+ * The batch-1 path shares the BatchNorm machinery above (conv-epilogue statistics rows -> ONE [4][C] block); its M tiles
+ * straddle samples, so at N > 1 the statistics come from the conv's raw NHWC output instead, sample = a grid dimension.
+ *
+ * Shared by the three entry points: raw is [N][HW][c_stride_raw]; workspace holds v2v_in_workspace_bytes(HW, C, N) bytes
+ * (8-byte aligned); tickets holds v2v_in_ticket_words(C, N) ints that are ZERO before the first launch and are re-armed
+ * in-kernel (a buffer must not be shared by launches that can run concurrently).  Reductions are two-stage in a fixed
+ * order with an fp64 combine, v2v_in_groups(HW, C, N) pixel groups per sample, no floating-point atomics: two runs give
+ * the same bits.  V2V_EINVAL for N <= 0, HW <= 0, C <= 0, a NULL tensor, c_stride_raw < C or misaligned strides. */
+int     v2v_in_groups(int64_t HW, int32_t C, int32_t N);
+int64_t v2v_in_workspace_bytes(int64_t HW, int32_t C, int32_t N);
+int     v2v_in_ticket_words(int32_t C, int32_t N);
+/* raw (raw_dtype V2V_F32, c_stride_raw % 4 == 0, or V2V_BF16 = V2V_OUT_RAW_ACT_NHWC, c_stride_raw % 8 == 0; 16-byte aligned)
+ * -> scale_shift [N][4][C] fp32: per sample the four rows of v2v_bn_finalize (scale, shift, mean, invstd).  gamma / beta
+ * may be NULL (affine=False, what the reference builds).  One launch: the last pixel group of a (sample, 64-channel slab)
+ * finalizes it. */
+int v2v_in_stats(const void* raw, int32_t raw_dtype, int32_t c_stride_raw, const float* gamma, const float* beta, float eps,
+                 float* scale_shift, void* workspace, int32_t* tickets, int32_t N, int64_t HW, int32_t C, void* stream);
+/* v2v_bn_apply / v2v_bn_apply_raw / v2v_bn_apply_x3 with the scale / shift rows of sample n = pixel / HW:
+ * y = act(raw * scale[n][c] + shift[n][c]) (+ add0) (+ add1), y / add0 / add1 NHWC `dtype` [N*HW][c_stride], channels >= C
+ * of y written 0.  x3: NULL, or (fp32, c_stride == C, C % 4 == 0) the bf16x3 operand [hi | lo | hi] of the result. */
+int v2v_in_apply(const void* raw, int32_t raw_dtype, int32_t c_stride_raw, const float* scale_shift,
+                 const void* add0, const void* add1, void* y, void* x3, int32_t N, int64_t HW, int32_t C, int32_t c_stride,
+                 int32_t act, float act_param, int32_t dtype, void* stream);
+/* v2v_bn_backward per sample (autograd of nn.InstanceNorm2d in training mode + ReLU / LeakyReLU):
+ * g = dY*act'(raw*scale[n]+shift[n]);  dRaw = scale[n]*(g - mean_p(g) - xhat*mean_p(g*xhat)) with the means over the
+ * sample's pixels and xhat from the sample's mean / invstd (stats: the [N][4][C] array of v2v_in_stats); raw is fp32.
+ * affine=True: dbeta (+)= sum_n sum_p g, dgamma (+)= sum_n sum_p g*xhat, added in sample order; both may be NULL. */
+int v2v_in_backward(const void* dy, const float* raw, int32_t c_stride_raw, const float* stats,
+                    void* draw, int32_t c_stride_out, float* dgamma, float* dbeta, int32_t accumulate,
+                    void* workspace, int32_t* tickets, int32_t N, int64_t HW, int32_t C, int32_t c_stride,
+                    int32_t act, float act_param, int32_t dtype, void* stream);
+
 /* AvgPool2d(3, stride 2, pad 1, count_include_pad=False) on planar fp32 [planes][H][W]
  * (build_pyr, models/base_model.py:122-134; MultiscaleDiscriminator.downsample :652). */
 int v2v_avgpool3s2_planar(const float* x, float* y, int64_t planes, int32_t H, int32_t W, void* stream);

@@ -104,13 +104,20 @@ class ConvFn(torch.autograd.Function):
                 OW = (W + 2 * cfg.pad - pc.KW) // pc.stride + 1
             cs_raw = (cout + 3) // 4 * 4
             raw = torch.empty(N * OH * OW * cs_raw, dtype=torch.float32, device=eng.device)
-            ss = torch.empty(4 * cout, dtype=torch.float32, device=eng.device)
-            raw, rows, shp = eng.conv(x, conv, cfg.pad_mode, cfg.pad, L.OUT_RAW_F32_NHWC, want_stats=True, out=raw,
-                                      label=cfg.label, fin=(norm, ss) if eng.fused_finalize else None)
             a0 = None if add0_t is None else Act(add0_t, cout)
             a1 = None if add1_t is None else Act(add1_t, cout)
-            y = eng.norm_apply(raw, rows, shp, cout, norm, cfg.act, cfg.act_param, add0=a0, add1=a1,
-                               label=cfg.label, ss=ss, finalized=eng.fused_finalize and eng.last_finalized)
+            if eng.inst_batched(norm, N):
+                # InstanceNorm2d at batch > 1: no statistics rows, no in-kernel finalize (both are batch-wide); the statistics
+                # saved for the backward pass are per sample, [N][4][C]
+                ss = torch.empty(N * 4 * cout, dtype=torch.float32, device=eng.device)
+                raw, _, shp = eng.conv(x, conv, cfg.pad_mode, cfg.pad, L.OUT_RAW_F32_NHWC, out=raw, label=cfg.label)
+                y = eng.inorm_apply(raw, shp, cout, norm, cfg.act, cfg.act_param, add0=a0, add1=a1, label=cfg.label, ss=ss)
+            else:
+                ss = torch.empty(4 * cout, dtype=torch.float32, device=eng.device)
+                raw, rows, shp = eng.conv(x, conv, cfg.pad_mode, cfg.pad, L.OUT_RAW_F32_NHWC, want_stats=True, out=raw,
+                                          label=cfg.label, fin=(norm, ss) if eng.fused_finalize else None)
+                y = eng.norm_apply(raw, rows, shp, cout, norm, cfg.act, cfg.act_param, add0=a0, add1=a1,
+                                   label=cfg.label, ss=ss, finalized=eng.fused_finalize and eng.last_finalized)
             ctx.shape = shp
             ctx.save_for_backward(x_t, raw, ss)
             return y.t
@@ -141,13 +148,19 @@ class ConvFn(torch.autograd.Function):
         if norm is not None:
             raw, ss = s1, s2
             g = torch.empty((N, OH, OW, cs_g), dtype=eng.tdtype, device=eng.device)
-            rows = lib.v2v_bn_backward_rows(P)
-            ws = eng.scratch("bn_bwd_ws", rows * 2 * cout + 2 * cout)
             affine = getattr(norm, "affine", False) and _live(norm.weight)
-            check(lib.v2v_bn_backward(_ptr(dy), _ptr(raw), (cout + 3) // 4 * 4, _ptr(ss), _ptr(g), cs_g,
-                                      _grad_ptr(norm.weight) if affine else None,
-                                      _grad_ptr(norm.bias) if affine else None, 1, _ptr(ws),
-                                      P, cout, dy.stride(2), cfg.act, cfg.act_param, dt, st), "bn_backward " + cfg.label)
+            dgamma = _grad_ptr(norm.weight) if affine else None
+            dbeta = _grad_ptr(norm.bias) if affine else None
+            if eng.inst_batched(norm, N):                     # per-sample statistics: ss is [N][4][C]
+                ws, tk = eng._in_scratch(N, OH * OW, cout)
+                check(lib.v2v_in_backward(_ptr(dy), _ptr(raw), (cout + 3) // 4 * 4, _ptr(ss), _ptr(g), cs_g, dgamma, dbeta, 1,
+                                          _ptr(ws), _ptr(tk), N, OH * OW, cout, dy.stride(2), cfg.act, cfg.act_param, dt, st),
+                      "in_backward " + cfg.label)
+            else:
+                rows = lib.v2v_bn_backward_rows(P)
+                ws = eng.scratch("bn_bwd_ws", rows * 2 * cout + 2 * cout)
+                check(lib.v2v_bn_backward(_ptr(dy), _ptr(raw), (cout + 3) // 4 * 4, _ptr(ss), _ptr(g), cs_g, dgamma, dbeta, 1, _ptr(ws),
+                                          P, cout, dy.stride(2), cfg.act, cfg.act_param, dt, st), "bn_backward " + cfg.label)
         else:
             y_t = s1
             if cfg.act == L.ACT_NONE and cfg.out_scale == 1.0 and not cfg.nchw:

@@ -1023,7 +1023,7 @@ class Engine:
             self.last_finalized = fin is not None
             if fin is not None:
                 norm, ss = fin
-                gamma, beta, eps, mom, rm, rv = self._norm_params(norm, N)
+                gamma, beta, eps, mom, rm, rv = self._batchwide_params(norm, N)
                 fin_counter = self._fin_counters.get((self._lane, self._sset))
                 if fin_counter is None:
                     # [0,128) finalize tickets per channel tile, [128,256) fused-norm departures, [256, 256 + 64 * 128) row-group tickets
@@ -1128,7 +1128,7 @@ class Engine:
         finalized = fin is not None and (fused is not None or N * H * W <= FUSE_FINALIZE_MAX_PIXELS)
         if finalized:
             norm, ss = fin
-            gamma, beta, eps, mom, rm, rv = self._norm_params(norm, N)
+            gamma, beta, eps, mom, rm, rv = self._batchwide_params(norm, N)
             key = (self._lane, self._sset)
             fin_counter = self._fin_counters.get(key)
             if fin_counter is None:
@@ -1334,7 +1334,7 @@ class Engine:
         for (raw, rows, fin), norm, ss, k, lbl in ((ra, norma, ssa, 0, labels[0]), (rb, normb, ssb, 1, labels[1])):
             if not fin:                                       # large layers: parallel two-stage finalize per member
                 with self.scratch_set(k):
-                    gamma, beta, eps, mom, rm, rv = self._norm_params(norm, N)
+                    gamma, beta, eps, mom, rm, rv = self._batchwide_params(norm, N)
                     st = self.scratch("stats", rows * cout * 2)
                     for t in (gamma, beta):
                         if t is not None:
@@ -1375,7 +1375,8 @@ class Engine:
             pm, po, c1a, n1a, ja = take(ma, 0)
             _, _, c1b, n1b, jb = take(mb, 0)
             na, nb = "%s.%d" % (name_a, first_index + k), "%s.%d" % (name_b, first_index + k)
-            if not self.pair_eligible(xa, c1a, xb, c1b):
+            # (per-sample InstanceNorm2d at batch > 1: the paired launches finalize batch-wide -> two independent chains)
+            if not self.pair_eligible(xa, c1a, xb, c1b) or self.inst_batched(n1a, xa.N) or self.inst_batched(n1b, xb.N):
                 xa = self.run_resblock(ba, xa, None, na)
                 xb = self.run_resblock(bb, xb, None, nb)
                 continue
@@ -1706,12 +1707,54 @@ class Engine:
                 norm._v2v_batches = getattr(norm, "_v2v_batches", 0) + 1     # -> num_batches_tracked at save time
             return gamma, beta, eps, mom, rm, rv
         if isinstance(norm, nn.InstanceNorm2d):
-            if N != 1:
-                raise NotImplementedError("InstanceNorm2d path supports batch 1 (per-sample statistics)")
+            # N > 1: the caller takes per-sample statistics (inst_batched / inorm_apply); batch-wide finalize paths are not eligible
             gamma = norm.weight.detach() if norm.affine else None
             beta = norm.bias.detach() if norm.affine else None
             return gamma, beta, norm.eps, 0.1, None, None
         raise NotImplementedError("norm layer %r" % type(norm))
+
+    @staticmethod
+    def inst_batched(norm, N):
+        """InstanceNorm2d at batch > 1: statistics per sample.  Such a group takes them from the conv's raw output
+        (v2v_in_stats -> v2v_in_apply, csrc/instance_norm.hip) and is not eligible for any path that finalizes the
+        statistics of the whole launch (fin=, fused-norm pair tiles, the persistent tiles' in-launch finalize)."""
+        return isinstance(norm, nn.InstanceNorm2d) and N > 1
+
+    def _batchwide_params(self, norm, N):
+        """_norm_params for a finalize over ALL N*OH*OW pixels of a launch: an error for a per-sample norm at batch > 1."""
+        if self.inst_batched(norm, N):
+            raise RuntimeError("InstanceNorm2d at batch %d reached a batch-wide statistics finalize (per-sample statistics needed)" % N)
+        return self._norm_params(norm, N)
+
+    def _in_scratch(self, N, HW, cout):
+        """(workspace, tickets) of the v2v_in_* launches on this lane / scratch sub-set (tickets start as zeros, re-armed in-kernel)."""
+        ws = self.scratch("in_ws", (lib.v2v_in_workspace_bytes(HW, cout, N) + 7) // 8, torch.float64)
+        tk = self.scratch("in_tickets", lib.v2v_in_ticket_words(cout, N), torch.int32, zero=True)
+        return ws, tk
+
+    def inorm_apply(self, raw, shape, cout, norm, act, act_param, add0=None, add1=None, label="", ss=None):
+        """InstanceNorm2d at batch > 1 on the conv's raw NHWC output: v2v_in_stats (per-sample [N][4][C] scale / shift /
+        mean / invstd into `ss`, kept by the caller for the backward pass on the training path) + v2v_in_apply."""
+        N, OH, OW = shape
+        raw_dt = L.BF16 if raw.dtype == torch.bfloat16 else L.F32      # Engine.conv(raw_act_ok=True): V2V_OUT_RAW_ACT_NHWC
+        cs_raw = (cout + 7) // 8 * 8 if raw_dt == L.BF16 else (cout + 3) // 4 * 4
+        if ss is None:
+            ss = self.scratch("in_scale_shift", N * 4 * cout)
+        gamma, beta, eps, _, _, _ = self._norm_params(norm, N)
+        ws, tk = self._in_scratch(N, OH * OW, cout)
+        for t in (gamma, beta, ss):
+            if t is not None:
+                self._keep(t)
+        check(lib.v2v_in_stats(_ptr(raw), raw_dt, cs_raw, _ptr(gamma), _ptr(beta), eps, _ptr(ss), _ptr(ws), _ptr(tk),
+                               N, OH * OW, cout, _stream()), "in_stats " + label)
+        self.label(label + ".norm")
+        y = self.empty_act(N, OH, OW, cout)
+        y3 = self._x3_out(y)
+        check(lib.v2v_in_apply(_ptr(raw), raw_dt, cs_raw, _ptr(ss), _ptr(None if add0 is None else add0.t),
+                               _ptr(None if add1 is None else add1.t), _ptr(y.t), _ptr(y3), N, OH * OW, cout, y.Cs,
+                               act, act_param, self.dtype, _stream()), "in_apply " + label)
+        self.label(label + ".apply")
+        return y
 
     def norm_apply(self, raw, rows, shape, cout, norm, act, act_param, add0=None, add1=None, label="", ss=None,
                    finalized=False):
@@ -1723,7 +1766,7 @@ class Engine:
         if ss is None:
             ss = self.scratch("scale_shift", 4 * cout)
         if not finalized:
-            gamma, beta, eps, mom, rm, rv = self._norm_params(norm, N)
+            gamma, beta, eps, mom, rm, rv = self._batchwide_params(norm, N)
             st = self.scratch("stats", rows * cout * 2)
             for t in (gamma, beta):
                 if t is not None:
@@ -1767,6 +1810,16 @@ class Engine:
             raw, rows, shp = self.onehot_conv(x, conv, label=label, fin=fin)
             return self.norm_apply(raw, rows, shp, conv.out_channels, norm, act, act_param, add0=add0, add1=add1, label=label,
                                    ss=ss, finalized=fin is not None)
+        if norm is not None and self.inst_batched(norm, x.N):
+            # per-sample statistics: the conv runs without statistics rows and without fin= (both are batch-wide)
+            if self._x3_ok(x, conv, pad_override, with_norm=False):
+                sub = self._x3_enter()
+                n0 = len(sub.conv_log)
+                raw, _, shp = sub.conv(self.split_x3(x), self._x3_wrap(conv), pad_mode, pad_override, L.OUT_RAW_F32_NHWC, label=label)
+                self._x3_log(sub, n0)
+            else:
+                raw, _, shp = self.conv(x, conv, pad_mode, pad_override, L.OUT_RAW_F32_NHWC, label=label, raw_act_ok=True)
+            return self.inorm_apply(raw, shp, conv.out_channels, norm, act, act_param, add0=add0, add1=add1, label=label)
         if norm is not None:
             ss = self.scratch("scale_shift", 4 * conv.out_channels)
             if self._x3_ok(x, conv, pad_override):

@@ -113,6 +113,12 @@ PROTOTYPES = {
     "v2v_bn_apply": (C.c_int, [_P, _I, _P, _P, _P, _P, _L, _I, _I, _I, _F, _I, _P]),
     "v2v_bn_apply_pair": (C.c_int, [_P] * 10 + [_I, _L, _I, _I, _I, _F, _I, _P]),
     "v2v_bn_apply_raw": (C.c_int, [_P, _I, _I, _P, _P, _P, _P, _L, _I, _I, _I, _F, _I, _P]),
+    "v2v_in_groups": (C.c_int, [_L, _I, _I]),
+    "v2v_in_workspace_bytes": (_L, [_L, _I, _I]),
+    "v2v_in_ticket_words": (C.c_int, [_I, _I]),
+    "v2v_in_stats": (C.c_int, [_P, _I, _I, _P, _P, _F, _P, _P, _P, _I, _L, _I, _P]),
+    "v2v_in_apply": (C.c_int, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _F, _I, _P]),
+    "v2v_in_backward": (C.c_int, [_P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I, _L, _I, _I, _I, _F, _I, _P]),
     "v2v_avgpool3s2_planar": (C.c_int, [_P, _P, _L, _I, _I, _P]),
     "v2v_avgpool3s2_nhwc": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "v2v_maxpool2_nhwc": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P]),
