@@ -214,6 +214,40 @@ int     v2v_conv_fused_norm_max_workgroups(void);
 int     v2v_fastdiv_magic(uint32_t d, uint32_t* m_out, int32_t* l_out);
 /* Tile configuration id the launch would use (after auto selection). */
 int     v2v_conv_tile_config(const v2v_conv_desc* d);
+/* The tile table (csrc/conv_tiles.h), one row per id v2v_conv_desc.tile accepts: rows 0 <= index < v2v_conv_tile_count(), each id once.
+ * Callers that choose tiles themselves (the Python engine's search) read what an id is from here instead of keeping their own list. */
+#define V2V_TILE_FAMILY_IGEMM   0   /* implicit GEMM, any conv: bm x bn, th = tw = 0                                              */
+#define V2V_TILE_FAMILY_PATCH   1   /* LDS-resident-patch 3x3 / stride 1: th x tw pixels x bn channels, as all families below      */
+#define V2V_TILE_FAMILY_PP      2   /* ... ping-pong wave groups                                                                    */
+#define V2V_TILE_FAMILY_PP2     3   /* ... ping-pong, second schedule                                                               */
+#define V2V_TILE_FAMILY_PP3     4   /* ... single-phase schedule                                                                    */
+#define V2V_TILE_FAMILY_S7      5   /* dense 7x7 / stride 1 / pad 3 on the single-phase kernel                                      */
+#define V2V_TILE_FAMILY_S2      6   /* 3x3 / stride 2                                                                               */
+#define V2V_TILE_FAMILY_T2      7   /* ConvTranspose2d(3x3, stride 2): th x tw INPUT positions                                      */
+#define V2V_TILE_FAMILY_ONE     8   /* persistent, weights-resident 3x3 / stride 1 for single-chunk layers                          */
+#define V2V_TILE_FAMILY_T2_ONE  9   /* ... its transposed stride-2 counterpart                                                      */
+#define V2V_TILE_FAMILY_HEAD    10  /* 7x7 / pad 3, <= 32 output channels                                                           */
+#define V2V_TILE_FAMILY_C8      11  /* 7x7 over 16-byte pixels                                                                      */
+#define V2V_TILE_FAMILY_ROWSUM  12  /* 7x7 generator heads as row GEMM + shifted sum                                                */
+#define V2V_TILE_GROUPED        1   /* v2v_conv2d_pair accepts it                                                                   */
+#define V2V_TILE_FUSED_NORM     2   /* V2V_OUT_NORM_ACT_NHWC accepted                                                               */
+#define V2V_TILE_PAD2           4   /* also the "full" 3x3 convolution (zero pad 2)                                                 */
+#define V2V_TILE_SINGLE_CHUNK   8   /* cin_stride of exactly one 128-byte chunk, no split-K                                         */
+#define V2V_TILE_PERSISTENT     16  /* one workgroup per compute unit walks the tiles: ONE statistics row per workgroup             */
+#define V2V_TILE_HELPER         32  /* has a weight-prefetch helper instance (v2v_conv_desc.prefetch)                               */
+#define V2V_TILE_BF16_ONLY      64
+#define V2V_TILE_ABLATION       128 /* instrumented copy of another tile (profiling)                                                */
+#define V2V_TILE_EXPERIMENT     256 /* not offered to a tile search by default                                                      */
+#define V2V_TILE_EXACT_BN       512 /* needs cout == bn                                                                             */
+struct v2v_conv_tile_info {    /* (a struct tag only: the name is the function's) */
+    int32_t id, family;     /* V2V_TILE_FAMILY_*                                                     */
+    int32_t bm, bn;         /* pixels x output channels of one workgroup's tile                      */
+    int32_t th, tw;         /* bm = th x tw (0, 0: implicit GEMM)                                    */
+    int32_t korder;         /* v2v_conv_desc.w_korder the tile reads: 0, 1 or 2                      */
+    int32_t flags;          /* V2V_TILE_* bits                                                       */
+};
+int     v2v_conv_tile_count(void);
+int     v2v_conv_tile_info(int32_t index, struct v2v_conv_tile_info* out);   /* V2V_EINVAL: index out of range */
 /* Launch.  nn.Conv2d / nn.ConvTranspose2d forward (models/networks.py:132-183 etc.), and -- with the
  * SAME parameter tensor packed in the opposite role -- their backward-data (autograd of F.conv2d /
  * F.conv_transpose2d in the reference):

@@ -798,7 +798,8 @@ static inline int launch_one_typed(int cfg, const ConvKArgs& k_in, int cus, hipS
     k.ablate = (k.ablate & 0xffff) | (stag << 16);
     if constexpr (std::is_same<T, bf16_t>::value) {
         if (cfg == 140) {
-            constexpr int TH = 8, TW = 32, BN = 64, NW = 8;
+            constexpr ConvTile t = conv_tile(140);
+            constexpr int TH = t.th, TW = t.tw, BN = t.bn, NW = 8;
             constexpr int GP = (((TH + 2) * (TW + 2) + 7) / 8 + NW - 1) / NW;
             const size_t lds = (size_t)9 * BN * 128 + (size_t)GP * NW * 1024 + (size_t)(4 * BN * 2 * 4 + NW * 4096);
             void (*kern)(const ConvKArgs) = conv3x3_one_kernel<T, TH, TW, BN>;
@@ -814,7 +815,9 @@ static inline int launch_one_typed(int cfg, const ConvKArgs& k_in, int cus, hipS
     }
     if constexpr (std::is_same<T, bf16_t>::value) {
         if (cfg == 141 || cfg == 143) {
-            constexpr int TH = 8, TW = 32, BN = 64, NW = 8;
+            constexpr ConvTile t = conv_tile(141), t3 = conv_tile(143);
+            static_assert(t.th == t3.th && t.tw == t3.tw && t.bn == t3.bn, "143 is 141's kernel with another store policy");
+            constexpr int TH = t.th, TW = t.tw, BN = t.bn, NW = 8;
             constexpr int NG = ((TH + 2) * (TW + 2) + 7) / 8;
             const size_t lds = (size_t)9 * BN * 128 + (size_t)2 * NG * 1024 + (size_t)(4 * BN * 2 * 4);
             void (*kern)(const ConvKArgs) = cfg == 143 ? conv3x3_one_db_kernel<T, TH, TW, BN, 2> : conv3x3_one_db_kernel<T, TH, TW, BN, 0>;
@@ -830,7 +833,8 @@ static inline int launch_one_typed(int cfg, const ConvKArgs& k_in, int cus, hipS
     }
     if constexpr (std::is_same<T, bf16_t>::value) {
         if (cfg == 114) {
-            constexpr int TH = 8, TW = 32, BN = 32, NW = 8;
+            constexpr ConvTile t = conv_tile(114);
+            constexpr int TH = t.th, TW = t.tw, BN = t.bn, NW = 8;
             constexpr int NG = ((TH + 1) * (TW + 1) + 7) / 8;
             const size_t lds = (size_t)9 * BN * 128 + (size_t)2 * NG * 1024 + (size_t)(NW * BN * 2 * 4);
             void (*kern)(const ConvKArgs) = conv3x3_t2_one_kernel<T, TH, TW, BN>;

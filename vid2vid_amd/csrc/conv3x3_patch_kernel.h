@@ -284,39 +284,24 @@ static int launch_patch_cfg(const ConvKArgs& k, hipStream_t s) {
     return check_launch();
 }
 
-// Patch-kernel tile configurations (ids >= 32; TH x TW output pixels x BN output channels)
-struct PatchCfg { int id, TH, TW, BN; };
-static const PatchCfg kPatchCfgs[] = {
-    {32, 2, 64, 64}, {33, 4, 64, 64}, {34, 2, 64, 128}, {35, 4, 32, 64}, {36, 8, 32, 64}, {37, 4, 32, 128},
-    // the same tiles with 2 dedicated loader waves
-    {40, 2, 64, 64}, {41, 4, 64, 64}, {42, 2, 64, 128}, {43, 4, 32, 64}, {44, 8, 32, 64}, {45, 4, 32, 128},
-    // 8 compute waves (2 per SIMD) + 2 loader waves (46, 47); 256 x 128 tile (48)
-    {46, 4, 64, 64}, {47, 2, 64, 128}, {48, 4, 64, 128},
-};
-static inline const PatchCfg* find_patch_cfg(int id) {
-    for (const PatchCfg& c : kPatchCfgs)
-        if (c.id == id) return &c;
-    return nullptr;
-}
-
 template <typename T>
 static inline int launch_patch_typed(int cfg, const ConvKArgs& k, hipStream_t s) {
     switch (cfg) {
-        case 32: return k.pf_dist > 0 ? launch_patch_cfg<T, 2, 64, 64, 2, 2, 5, 0, 1>(k, s) : launch_patch_cfg<T, 2, 64, 64, 2, 2, 5, 0, 0>(k, s);    // 128 px x  64, wave tile 64x32, 114 KiB
-        case 33: return k.pf_dist > 0 ? launch_patch_cfg<T, 4, 64, 64, 4, 1, 5, 0, 1>(k, s) : launch_patch_cfg<T, 4, 64, 64, 4, 1, 5, 0, 0>(k, s);    // 256 px x  64, wave tile 64x64, 144 KiB
-        case 34: return k.pf_dist > 0 ? launch_patch_cfg<T, 2, 64, 128, 2, 2, 5, 0, 1>(k, s) : launch_patch_cfg<T, 2, 64, 128, 2, 2, 5, 0, 0>(k, s);   // 128 px x 128, wave tile 64x64, 152 KiB
-        case 35: return k.pf_dist > 0 ? launch_patch_cfg<T, 4, 32, 64, 2, 2, 5, 0, 1>(k, s) : launch_patch_cfg<T, 4, 32, 64, 2, 2, 5, 0, 0>(k, s);    // 128 px x  64 for W % 64 != 0
-        case 36: return k.pf_dist > 0 ? launch_patch_cfg<T, 8, 32, 64, 4, 1, 5, 0, 1>(k, s) : launch_patch_cfg<T, 8, 32, 64, 4, 1, 5, 0, 0>(k, s);    // 256 px x  64
-        case 37: return k.pf_dist > 0 ? launch_patch_cfg<T, 4, 32, 128, 2, 2, 5, 0, 1>(k, s) : launch_patch_cfg<T, 4, 32, 128, 2, 2, 5, 0, 0>(k, s);   // 128 px x 128
-        case 40: return launch_patch_cfg<T, 2, 64, 64, 2, 2, 5, 2, 0>(k, s);
-        case 41: return launch_patch_cfg<T, 4, 64, 64, 4, 1, 5, 2, 0>(k, s);
-        case 42: return launch_patch_cfg<T, 2, 64, 128, 2, 2, 5, 2, 0>(k, s);
-        case 43: return launch_patch_cfg<T, 4, 32, 64, 2, 2, 5, 2, 0>(k, s);
-        case 44: return launch_patch_cfg<T, 8, 32, 64, 4, 1, 5, 2, 0>(k, s);
-        case 45: return launch_patch_cfg<T, 4, 32, 128, 2, 2, 5, 2, 0>(k, s);
-        case 46: return launch_patch_cfg<T, 4, 64, 64, 4, 2, 5, 2, 0>(k, s);    // 256 px x  64, 8 compute waves (64x32)
-        case 47: return launch_patch_cfg<T, 2, 64, 128, 2, 4, 5, 2, 0>(k, s);   // 128 px x 128, 8 compute waves (64x32)
-        case 48: return launch_patch_cfg<T, 4, 64, 128, 4, 1, 3, 2, 0>(k, s);   // 256 px x 128, 4 compute waves (64x128), 3-deep ring
+        case 32: return k.pf_dist > 0 ? launch_patch_cfg<T, V2V_TILE_GEOM(32), 2, 2, 5, 0, 1>(k, s) : launch_patch_cfg<T, V2V_TILE_GEOM(32), 2, 2, 5, 0, 0>(k, s);    // 128 px x  64, wave tile 64x32, 114 KiB
+        case 33: return k.pf_dist > 0 ? launch_patch_cfg<T, V2V_TILE_GEOM(33), 4, 1, 5, 0, 1>(k, s) : launch_patch_cfg<T, V2V_TILE_GEOM(33), 4, 1, 5, 0, 0>(k, s);    // 256 px x  64, wave tile 64x64, 144 KiB
+        case 34: return k.pf_dist > 0 ? launch_patch_cfg<T, V2V_TILE_GEOM(34), 2, 2, 5, 0, 1>(k, s) : launch_patch_cfg<T, V2V_TILE_GEOM(34), 2, 2, 5, 0, 0>(k, s);   // 128 px x 128, wave tile 64x64, 152 KiB
+        case 35: return k.pf_dist > 0 ? launch_patch_cfg<T, V2V_TILE_GEOM(35), 2, 2, 5, 0, 1>(k, s) : launch_patch_cfg<T, V2V_TILE_GEOM(35), 2, 2, 5, 0, 0>(k, s);    // 128 px x  64 for W % 64 != 0
+        case 36: return k.pf_dist > 0 ? launch_patch_cfg<T, V2V_TILE_GEOM(36), 4, 1, 5, 0, 1>(k, s) : launch_patch_cfg<T, V2V_TILE_GEOM(36), 4, 1, 5, 0, 0>(k, s);    // 256 px x  64
+        case 37: return k.pf_dist > 0 ? launch_patch_cfg<T, V2V_TILE_GEOM(37), 2, 2, 5, 0, 1>(k, s) : launch_patch_cfg<T, V2V_TILE_GEOM(37), 2, 2, 5, 0, 0>(k, s);   // 128 px x 128
+        case 40: return launch_patch_cfg<T, V2V_TILE_GEOM(40), 2, 2, 5, 2, 0>(k, s);
+        case 41: return launch_patch_cfg<T, V2V_TILE_GEOM(41), 4, 1, 5, 2, 0>(k, s);
+        case 42: return launch_patch_cfg<T, V2V_TILE_GEOM(42), 2, 2, 5, 2, 0>(k, s);
+        case 43: return launch_patch_cfg<T, V2V_TILE_GEOM(43), 2, 2, 5, 2, 0>(k, s);
+        case 44: return launch_patch_cfg<T, V2V_TILE_GEOM(44), 4, 1, 5, 2, 0>(k, s);
+        case 45: return launch_patch_cfg<T, V2V_TILE_GEOM(45), 2, 2, 5, 2, 0>(k, s);
+        case 46: return launch_patch_cfg<T, V2V_TILE_GEOM(46), 4, 2, 5, 2, 0>(k, s);    // 256 px x  64, 8 compute waves (64x32)
+        case 47: return launch_patch_cfg<T, V2V_TILE_GEOM(47), 2, 4, 5, 2, 0>(k, s);   // 128 px x 128, 8 compute waves (64x32)
+        case 48: return launch_patch_cfg<T, V2V_TILE_GEOM(48), 4, 1, 3, 2, 0>(k, s);   // 256 px x 128, 4 compute waves (64x128), 3-deep ring
     }
     set_error("conv: unknown patch tile config %d", cfg);
     return V2V_EINVAL;

@@ -331,28 +331,17 @@ static int launch_pp2_cfg(const ConvKArgs& k, int groups, hipStream_t s) {
     return check_launch();
 }
 
-// second-schedule ping-pong tile configurations (ids 70..75)
-static const PatchCfg kPp2Cfgs[] = {
-    {70, 8, 32, 64}, {71, 8, 32, 128}, {72, 8, 32, 64}, {73, 4, 64, 64}, {74, 4, 64, 64}, {75, 4, 32, 128},
-    {78, 8, 32, 128}, {79, 8, 32, 64},     // ablation instances of 71 / 70 (scripts/pp2_ablate.py)
-};
-static inline const PatchCfg* find_pp2_cfg(int id) {
-    for (const PatchCfg& c : kPp2Cfgs)
-        if (c.id == id) return &c;
-    return nullptr;
-}
-
 template <typename T>
 static inline int launch_pp2_typed(int cfg, const ConvKArgs& k, int groups, hipStream_t s) {
     switch (cfg) {
-        case 70: return launch_pp2_cfg<T, 8, 32, 64, 5>(k, groups, s);    // 256 px x  64, wave tile 64x32, 5-deep weight ring, 136 KiB
-        case 71: return launch_pp2_cfg<T, 8, 32, 128, 4>(k, groups, s);   // 256 px x 128, wave tile 64x64, 160 KiB
-        case 72: return launch_pp2_cfg<T, 8, 32, 64, 4>(k, groups, s);    // as 70 with the 4-deep ring, 128 KiB
-        case 73: return launch_pp2_cfg<T, 4, 64, 64, 5>(k, groups, s);    // 256 px x  64 for 64-wide tiles, 152 KiB
-        case 74: return launch_pp2_cfg<T, 4, 64, 64, 4>(k, groups, s);
-        case 75: return launch_pp2_cfg<T, 4, 32, 128, 5>(k, groups, s);   // 128 px x 128, wave tile 32x64
-        case 78: return launch_pp2_cfg<T, 8, 32, 128, 4, 1>(k, groups, s);
-        case 79: return launch_pp2_cfg<T, 8, 32, 64, 5, 1>(k, groups, s);
+        case 70: return launch_pp2_cfg<T, V2V_TILE_GEOM(70), 5>(k, groups, s);    // 256 px x  64, wave tile 64x32, 5-deep weight ring, 136 KiB
+        case 71: return launch_pp2_cfg<T, V2V_TILE_GEOM(71), 4>(k, groups, s);   // 256 px x 128, wave tile 64x64, 160 KiB
+        case 72: return launch_pp2_cfg<T, V2V_TILE_GEOM(72), 4>(k, groups, s);    // as 70 with the 4-deep ring, 128 KiB
+        case 73: return launch_pp2_cfg<T, V2V_TILE_GEOM(73), 5>(k, groups, s);    // 256 px x  64 for 64-wide tiles, 152 KiB
+        case 74: return launch_pp2_cfg<T, V2V_TILE_GEOM(74), 4>(k, groups, s);
+        case 75: return launch_pp2_cfg<T, V2V_TILE_GEOM(75), 5>(k, groups, s);   // 128 px x 128, wave tile 32x64
+        case 78: return launch_pp2_cfg<T, V2V_TILE_GEOM(78), 4, 1>(k, groups, s);
+        case 79: return launch_pp2_cfg<T, V2V_TILE_GEOM(79), 5, 1>(k, groups, s);
     }
     set_error("conv: unknown ping-pong (schedule 2) tile config %d", cfg);
     return V2V_EINVAL;

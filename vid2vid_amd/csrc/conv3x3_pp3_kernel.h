@@ -505,60 +505,38 @@ static int launch_pp3_cfg(const ConvKArgs& k, int groups, hipStream_t s) {
     return check_launch();
 }
 
-// single-phase tile configurations (ids 80..93)
-static const PatchCfg kPp3Cfgs[] = {
-    {80, 8, 32, 64}, {81, 8, 32, 128}, {82, 8, 32, 64}, {83, 4, 64, 64}, {84, 4, 32, 128}, {85, 4, 64, 128},
-    {86, 4, 32, 128}, {87, 2, 64, 128},     // 4 waves (2 x 2), 64 x 64 wave tiles
-    {88, 8, 32, 128}, {89, 8, 32, 64},     // ablation instances of 81 / 80
-    {90, 8, 32, 64}, {91, 4, 64, 64},      // K pairs: 4 x 1 wave tiles of 64 x 64, two K halves (see the kernel comment)
-    {92, 8, 32, 64}, {93, 4, 64, 64},      // K quads: 2 x 1 wave tiles of 128 x 64, four K quarters: 6 reads per 8 MFMAs
-    {94, 8, 32, 64}, {95, 4, 64, 64},      // single-chunk layers: one patch buffer, 72 / 80 KiB
-    // (round 6: the round-5 experiment tiles 97-99 / 130-132 -- one barrier per two / three steps, deeper weight rings, static wave
-    //  priority on tile 90's geometry, all bit-identical to tile 90 and none faster, DESIGN 3.1 -- are no longer instantiated; the
-    //  FLAGS parameter of the body that built them stays)
-    {140, 8, 32, 64}, {141, 8, 32, 64}, {143, 8, 32, 64},    // conv3x3_one_kernel.h: persistent, weights-resident single-chunk tile (geometry only; launched by launch_one_typed)
-    {96, 4, 32, 64},                       // single-chunk layers, FOUR waves (2 x 2, 64 x 32 wave tiles), 28 + 24 = 52 KiB, 167 + 32 registers: the
-                                           // tile that really puts two workgroups on a CU (staged for round 5; 94 / 95 never did: DESIGN 3.6 item 15)
-    {120, 4, 32, 64}, {121, 4, 32, 128},   // 7x7 window (staged for round 5): 10 x 38 pixel patch, 49 tap steps per channel chunk
-};
-static inline const PatchCfg* find_pp3_cfg(int id) {
-    for (const PatchCfg& c : kPp3Cfgs)
-        if (c.id == id) return &c;
-    return nullptr;
-}
-
 template <typename T>
 static inline int launch_pp3_typed(int cfg, const ConvKArgs& k, int groups, hipStream_t s) {
     switch (cfg) {
-        case 80: return launch_pp3_cfg<T, 8, 32, 64, 4>(k, groups, s);    // 256 px x  64, wave tile 64x32, 4 slices in flight, 128 KiB
-        case 81: return launch_pp3_cfg<T, 8, 32, 128, 4>(k, groups, s);   // 256 px x 128, wave tile 64x64, 160 KiB
-        case 82: return launch_pp3_cfg<T, 8, 32, 64, 5>(k, groups, s);    // as 80, 5 slices in flight, 136 KiB
-        case 83: return launch_pp3_cfg<T, 4, 64, 64, 4>(k, groups, s);    // 256 px x  64 for 64-wide tiles, 144 KiB
-        case 84: return launch_pp3_cfg<T, 4, 32, 128, 4>(k, groups, s);   // 128 px x 128, wave tile 32x64
-        case 85: return launch_pp3_cfg<T, 4, 64, 128, 3>(k, groups, s);   // 256 px x 128 for 64-wide tiles, 3 slices, 160 KiB
-        case 86: return launch_pp3_cfg<T, 4, 32, 128, 4, 0, 2, 2>(k, groups, s);   // 128 px x 128, FOUR waves, wave tile 64x64, 120 KiB
-        case 87: return launch_pp3_cfg<T, 2, 64, 128, 4, 0, 2, 2>(k, groups, s);   // same for 64-wide tile rows
-        case 90: return launch_pp3_cfg<T, 8, 32, 64, 5, 0, 4, 1, 2>(k, groups, s);   // as 82 (256 px x 64, 5 slices), K pairs: 8 reads per 8 MFMAs
-        case 91: return launch_pp3_cfg<T, 4, 64, 64, 4, 0, 4, 1, 2>(k, groups, s);   // as 83 for 64-wide tile rows
-        case 92: return launch_pp3_cfg<T, 8, 32, 64, 5, 0, 2, 1, 4>(k, groups, s);   // as 82, K quads
-        case 93: return launch_pp3_cfg<T, 4, 64, 64, 4, 0, 2, 1, 4>(k, groups, s);   // as 83, K quads
+        case 80: return launch_pp3_cfg<T, V2V_TILE_GEOM(80), 4>(k, groups, s);    // 256 px x  64, wave tile 64x32, 4 slices in flight, 128 KiB
+        case 81: return launch_pp3_cfg<T, V2V_TILE_GEOM(81), 4>(k, groups, s);   // 256 px x 128, wave tile 64x64, 160 KiB
+        case 82: return launch_pp3_cfg<T, V2V_TILE_GEOM(82), 5>(k, groups, s);    // as 80, 5 slices in flight, 136 KiB
+        case 83: return launch_pp3_cfg<T, V2V_TILE_GEOM(83), 4>(k, groups, s);    // 256 px x  64 for 64-wide tiles, 144 KiB
+        case 84: return launch_pp3_cfg<T, V2V_TILE_GEOM(84), 4>(k, groups, s);   // 128 px x 128, wave tile 32x64
+        case 85: return launch_pp3_cfg<T, V2V_TILE_GEOM(85), 3>(k, groups, s);   // 256 px x 128 for 64-wide tiles, 3 slices, 160 KiB
+        case 86: return launch_pp3_cfg<T, V2V_TILE_GEOM(86), 4, 0, 2, 2>(k, groups, s);   // 128 px x 128, FOUR waves, wave tile 64x64, 120 KiB
+        case 87: return launch_pp3_cfg<T, V2V_TILE_GEOM(87), 4, 0, 2, 2>(k, groups, s);   // same for 64-wide tile rows
+        case 90: return launch_pp3_cfg<T, V2V_TILE_GEOM(90), 5, 0, 4, 1, 2>(k, groups, s);   // as 82 (256 px x 64, 5 slices), K pairs: 8 reads per 8 MFMAs
+        case 91: return launch_pp3_cfg<T, V2V_TILE_GEOM(91), 4, 0, 4, 1, 2>(k, groups, s);   // as 83 for 64-wide tile rows
+        case 92: return launch_pp3_cfg<T, V2V_TILE_GEOM(92), 5, 0, 2, 1, 4>(k, groups, s);   // as 82, K quads
+        case 93: return launch_pp3_cfg<T, V2V_TILE_GEOM(93), 4, 0, 2, 1, 4>(k, groups, s);   // as 83, K quads
         case 120: case 121:                // 7x7 window: bf16 only for now (the fp32 instantiations double an 8-minute translation unit)
             if constexpr (std::is_same<T, bf16_t>::value) {
-                if (cfg == 120) return launch_pp3_cfg<T, 4, 32, 64, 4, 0, 4, 2, 1, false, 7>(k, 1, s);    // 128 px x  64, 2 x 48 + 32 = 128 KiB, 109 registers
-                return launch_pp3_cfg<T, 4, 32, 128, 3, 0, 4, 2, 1, false, 7>(k, 1, s);                   // 128 px x 128, 2 x 48 + 48 = 144 KiB, 163 registers
+                if (cfg == 120) return launch_pp3_cfg<T, V2V_TILE_GEOM(120), 4, 0, 4, 2, 1, false, 7>(k, 1, s);    // 128 px x  64, 2 x 48 + 32 = 128 KiB, 109 registers
+                return launch_pp3_cfg<T, V2V_TILE_GEOM(121), 3, 0, 4, 2, 1, false, 7>(k, 1, s);                   // 128 px x 128, 2 x 48 + 48 = 144 KiB, 163 registers
             }
             break;
         case 96:                           // single-chunk, four waves: two co-resident workgroups per CU by registers (2 waves / SIMD) and LDS (52 KiB)
-            if constexpr (std::is_same<T, bf16_t>::value) return launch_pp3_cfg<T, 4, 32, 64, 3, 0, 2, 2, 1, true>(k, 1, s);
+            if constexpr (std::is_same<T, bf16_t>::value) return launch_pp3_cfg<T, V2V_TILE_GEOM(96), 3, 0, 2, 2, 1, true>(k, 1, s);
             break;
         case 94: case 95:                  // single-chunk tiles: bf16 only (64 input channels = one 128-byte chunk), single launches only
             if constexpr (std::is_same<T, bf16_t>::value) {
-                if (cfg == 94) return launch_pp3_cfg<T, 8, 32, 64, 3, 0, 4, 2, 1, true>(k, 1, s);   // as 80 with 3 slices: 48 + 24 KiB
-                return launch_pp3_cfg<T, 4, 64, 64, 3, 0, 4, 2, 1, true>(k, 1, s);                  // as 83 with 3 slices: 56 + 24 KiB
+                if (cfg == 94) return launch_pp3_cfg<T, V2V_TILE_GEOM(94), 3, 0, 4, 2, 1, true>(k, 1, s);   // as 80 with 3 slices: 48 + 24 KiB
+                return launch_pp3_cfg<T, V2V_TILE_GEOM(95), 3, 0, 4, 2, 1, true>(k, 1, s);                  // as 83 with 3 slices: 56 + 24 KiB
             }
             break;
-        case 88: return launch_pp3_cfg<T, 8, 32, 128, 4, 1>(k, groups, s);
-        case 89: return launch_pp3_cfg<T, 8, 32, 64, 4, 1>(k, groups, s);
+        case 88: return launch_pp3_cfg<T, V2V_TILE_GEOM(88), 4, 1>(k, groups, s);
+        case 89: return launch_pp3_cfg<T, V2V_TILE_GEOM(89), 4, 1>(k, groups, s);
     }
     set_error("conv: unknown single-phase tile config %d", cfg);
     return V2V_EINVAL;

@@ -270,28 +270,17 @@ static int launch_pp_cfg(const ConvKArgs& k, hipStream_t s) {
     return check_launch();
 }
 
-// ping-pong tile configurations (ids 50..55)
-static const PatchCfg kPpCfgs[] = {
-    {50, 4, 64, 128}, {51, 4, 64, 64}, {52, 2, 64, 128}, {53, 8, 32, 128}, {54, 8, 32, 64}, {55, 4, 32, 128},
-    {56, 8, 32, 64}, {57, 4, 64, 64},
-};
-static inline const PatchCfg* find_pp_cfg(int id) {
-    for (const PatchCfg& c : kPpCfgs)
-        if (c.id == id) return &c;
-    return nullptr;
-}
-
 template <typename T>
 static inline int launch_pp_typed(int cfg, const ConvKArgs& k, hipStream_t s) {
     switch (cfg) {
-        case 50: return launch_pp_cfg<T, 4, 64, 128, 3>(k, s);   // 256 px x 128, wave tile 64x64, 160 KiB
-        case 51: return launch_pp_cfg<T, 4, 64, 64, 4>(k, s);    // 256 px x  64, wave tile 64x32, 4-deep weight ring
-        case 52: return launch_pp_cfg<T, 2, 64, 128, 4>(k, s);   // 128 px x 128, wave tile 32x64
-        case 53: return launch_pp_cfg<T, 8, 32, 128, 4>(k, s);   // 256 px x 128 for 32-wide tiles
-        case 54: return launch_pp_cfg<T, 8, 32, 64, 4>(k, s);
-        case 55: return launch_pp_cfg<T, 4, 32, 128, 4>(k, s);
-        case 56: return launch_pp_cfg<T, 8, 32, 64, 3>(k, s);    // as 54 with the 3-deep ring
-        case 57: return launch_pp_cfg<T, 4, 64, 64, 3>(k, s);    // as 51 with the 3-deep ring
+        case 50: return launch_pp_cfg<T, V2V_TILE_GEOM(50), 3>(k, s);   // 256 px x 128, wave tile 64x64, 160 KiB
+        case 51: return launch_pp_cfg<T, V2V_TILE_GEOM(51), 4>(k, s);    // 256 px x  64, wave tile 64x32, 4-deep weight ring
+        case 52: return launch_pp_cfg<T, V2V_TILE_GEOM(52), 4>(k, s);   // 128 px x 128, wave tile 32x64
+        case 53: return launch_pp_cfg<T, V2V_TILE_GEOM(53), 4>(k, s);   // 256 px x 128 for 32-wide tiles
+        case 54: return launch_pp_cfg<T, V2V_TILE_GEOM(54), 4>(k, s);
+        case 55: return launch_pp_cfg<T, V2V_TILE_GEOM(55), 4>(k, s);
+        case 56: return launch_pp_cfg<T, V2V_TILE_GEOM(56), 3>(k, s);    // as 54 with the 3-deep ring
+        case 57: return launch_pp_cfg<T, V2V_TILE_GEOM(57), 3>(k, s);    // as 51 with the 3-deep ring
     }
     set_error("conv: unknown ping-pong tile config %d", cfg);
     return V2V_EINVAL;

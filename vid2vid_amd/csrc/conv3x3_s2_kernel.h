@@ -310,21 +310,13 @@ static int launch_s2_cfg(const ConvKArgs& k, hipStream_t s) {
     return check_launch();
 }
 
-// stride-2 patch tile configurations (ids 100..103)
-static const PatchCfg kS2Cfgs[] = {{100, 4, 32, 64}, {101, 4, 32, 128}, {102, 4, 32, 64}, {103, 4, 32, 128}};
-static inline const PatchCfg* find_s2_cfg(int id) {
-    for (const PatchCfg& c : kS2Cfgs)
-        if (c.id == id) return &c;
-    return nullptr;
-}
-
 template <typename T>
 static inline int launch_s2_typed(int cfg, const ConvKArgs& k, hipStream_t s) {
     switch (cfg) {
-        case 100: return launch_s2_cfg<T, 4, 32, 64, 4>(k, s);     // 128 px x  64, 4 slices in flight, 112 KiB
-        case 101: return launch_s2_cfg<T, 4, 32, 128, 4>(k, s);    // 128 px x 128, wave tile 32 x 64, 144 KiB
-        case 102: return launch_s2_cfg<T, 4, 32, 64, 3>(k, s);     // as 100, 3 slices, 104 KiB
-        case 103: return launch_s2_cfg<T, 4, 32, 128, 3>(k, s);    // as 101, 3 slices, 128 KiB
+        case 100: return launch_s2_cfg<T, V2V_TILE_GEOM(100), 4>(k, s);     // 128 px x  64, 4 slices in flight, 112 KiB
+        case 101: return launch_s2_cfg<T, V2V_TILE_GEOM(101), 4>(k, s);    // 128 px x 128, wave tile 32 x 64, 144 KiB
+        case 102: return launch_s2_cfg<T, V2V_TILE_GEOM(102), 3>(k, s);     // as 100, 3 slices, 104 KiB
+        case 103: return launch_s2_cfg<T, V2V_TILE_GEOM(103), 3>(k, s);    // as 101, 3 slices, 128 KiB
     }
     set_error("conv: unknown stride-2 patch tile config %d", cfg);
     return V2V_EINVAL;

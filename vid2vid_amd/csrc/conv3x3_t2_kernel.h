@@ -283,22 +283,13 @@ static int launch_t2_cfg(const ConvKArgs& k, hipStream_t s) {
     return check_launch();
 }
 
-// transposed stride-2 patch tile configurations (ids 110..113): (TH, TW) = tile of INPUT positions
-static const PatchCfg kT2Cfgs[] = {{110, 4, 32, 64}, {111, 4, 32, 128}, {112, 8, 32, 64}, {113, 4, 32, 64},
-                                   {114, 8, 32, 32}};    // 114: geometry only -- the persistent kernel of conv3x3_one_kernel.h (launch_one_typed)
-static inline const PatchCfg* find_t2_cfg(int id) {
-    for (const PatchCfg& c : kT2Cfgs)
-        if (c.id == id) return &c;
-    return nullptr;
-}
-
 template <typename T>
 static inline int launch_t2_typed(int cfg, const ConvKArgs& k, hipStream_t s) {
     switch (cfg) {
-        case 110: return launch_t2_cfg<T, 4, 32, 64, 4>(k, s);     // 128 positions x  64 channels x 4 classes, 80 KiB (two workgroups per CU)
-        case 111: return launch_t2_cfg<T, 4, 32, 128, 4>(k, s);    // 128 positions x 128 channels, 112 KiB
-        case 112: return launch_t2_cfg<T, 8, 32, 64, 4>(k, s);     // 256 positions x  64 channels, wave tile 64 x 32 per class, 112 KiB
-        case 113: return launch_t2_cfg<T, 4, 32, 64, 3>(k, s);     // as 110, 3 slices in flight, 72 KiB
+        case 110: return launch_t2_cfg<T, V2V_TILE_GEOM(110), 4>(k, s);     // 128 positions x  64 channels x 4 classes, 80 KiB (two workgroups per CU)
+        case 111: return launch_t2_cfg<T, V2V_TILE_GEOM(111), 4>(k, s);    // 128 positions x 128 channels, 112 KiB
+        case 112: return launch_t2_cfg<T, V2V_TILE_GEOM(112), 4>(k, s);     // 256 positions x  64 channels, wave tile 64 x 32 per class, 112 KiB
+        case 113: return launch_t2_cfg<T, V2V_TILE_GEOM(113), 3>(k, s);     // as 110, 3 slices in flight, 72 KiB
     }
     set_error("conv: unknown transposed stride-2 patch tile config %d", cfg);
     return V2V_EINVAL;

@@ -57,23 +57,6 @@ namespace v2v {
 // -------------------------------------------------------------------------------------
 // host side
 // -------------------------------------------------------------------------------------
-struct TileCfg { int id, BM, BN; };
-static const TileCfg kCfgs[] = {
-    {1, 128, 128}, {2, 128, 64}, {3, 64, 64}, {4, 128, 32}, {5, 64, 128}, {6, 256, 64},
-    {7, 128, 64}, {8, 128, 128},      // deeper LDS-DMA rings of 2 / 1
-    {9, 64, 64}, {10, 64, 64}, {11, 128, 64}, {12, 64, 128},   // occupancy / depth variants of 3, 2, 5
-    {13, 128, 64}, {14, 128, 128}, {15, 128, 128}, {16, 256, 64}, {17, 64, 128},   // 8-wave workgroups
-    // wave tiles >= 64x64 (LDS-read efficient); meant to be combined with split-K on small-M layers
-    {18, 256, 128}, {19, 256, 128}, {20, 128, 256}, {21, 128, 128}, {22, 256, 128}, {23, 128, 256},
-};
-static const int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
-
-static const TileCfg* find_cfg(int id) {
-    for (int i = 0; i < kNumCfgs; ++i)
-        if (kCfgs[i].id == id) return &kCfgs[i];
-    return nullptr;
-}
-
 static int bke_of(int dtype) { return dtype == V2V_BF16 ? 64 : 32; }
 
 // taps of transposed-conv output class `par` (output index = stride*i + par) along one axis:
@@ -390,7 +373,6 @@ static int device_cus() {
 }
 int launch_conv_bf16(int cfg, const ConvKArgs& k, int ncls, hipStream_t s);
 int launch_conv_f32(int cfg, const ConvKArgs& k, int ncls, hipStream_t s);
-bool conv_cfg_has_helper(int cfg);
 int launch_patch_bf16(int cfg, const ConvKArgs& k, hipStream_t s);
 int launch_patch_f32(int cfg, const ConvKArgs& k, hipStream_t s);
 int launch_pp_bf16(int cfg, const ConvKArgs& k, hipStream_t s);
@@ -414,8 +396,8 @@ int launch_c8_f32(const ConvKArgs& k, hipStream_t s);
 static int choose_cfg(long long Mc, int cout, int ncls) {
     if (cout <= 32) return 4;
     auto tiles = [&](int id) {
-        const TileCfg* c = find_cfg(id);
-        return ceil_div(Mc, c->BM) * ceil_div(cout, c->BN) * ncls;
+        const ConvTile* c = find_conv_tile(id);
+        return ceil_div(Mc, c->bm) * ceil_div(cout, c->bn) * ncls;
     };
     if (cout <= 64) return tiles(2) >= 512 ? 2 : 3;
     if (tiles(1) >= 448) return 1;
@@ -427,22 +409,27 @@ static unsigned long long* g_conv_dbg_clocks = nullptr;    // v2v_conv_debug_clo
 
 struct ConvOp : Op {
     ConvKArgs k;
-    int ncls, cfg, dtype;
+    const ConvTile* tile = nullptr;      // row of the tile table (conv_tiles.h), found once by build_conv
+    int ncls, dtype;
     long long slab_bytes; int sk_tickets;
     int groups = 1;      // 2: grouped launch (v2v_conv2d_pair), second member's tensors in k.g1
     int launch(hipStream_t s) override {
-        if (cfg >= 140 || cfg == 114) return launch_one_bf16(cfg, k, device_cus(), s);     // persistent, weights-resident single-chunk tiles (bf16: host check); 114: the transposed stride-2 one
-        if (cfg >= 120) return dtype == V2V_BF16 ? launch_pp3_bf16(cfg, k, 1, s) : launch_pp3_f32(cfg, k, 1, s);    // 7x7 window on the single-phase kernel
-        if (cfg >= 110) return dtype == V2V_BF16 ? launch_t2_bf16(cfg, k, s) : launch_t2_f32(cfg, k, s);
-        if (cfg >= 100) return dtype == V2V_BF16 ? launch_s2_bf16(cfg, k, s) : launch_s2_f32(cfg, k, s);
-        if (cfg >= 80) return dtype == V2V_BF16 ? launch_pp3_bf16(cfg, k, groups, s) : launch_pp3_f32(cfg, k, groups, s);
-        if (cfg >= 70) return dtype == V2V_BF16 ? launch_pp2_bf16(cfg, k, groups, s) : launch_pp2_f32(cfg, k, groups, s);
-        if (cfg == 62) return launch_rowsum_bf16(k, s);
-        if (cfg == 61) return dtype == V2V_BF16 ? launch_c8_bf16(k, s) : launch_c8_f32(k, s);
-        if (cfg == 60) return dtype == V2V_BF16 ? launch_head_bf16(k, s) : launch_head_f32(k, s);
-        if (cfg >= 50) return dtype == V2V_BF16 ? launch_pp_bf16(cfg, k, s) : launch_pp_f32(cfg, k, s);
-        if (cfg >= 32) return dtype == V2V_BF16 ? launch_patch_bf16(cfg, k, s) : launch_patch_f32(cfg, k, s);
-        return dtype == V2V_BF16 ? launch_conv_bf16(cfg, k, ncls, s) : launch_conv_f32(cfg, k, ncls, s);
+        const bool bf = dtype == V2V_BF16;
+        const int cfg = tile->id;
+        switch (tile->family) {
+            case V2V_TILE_FAMILY_ONE: case V2V_TILE_FAMILY_T2_ONE: return launch_one_bf16(cfg, k, device_cus(), s);     // persistent, weights-resident single-chunk tiles (bf16: host check)
+            case V2V_TILE_FAMILY_S7:     return bf ? launch_pp3_bf16(cfg, k, 1, s) : launch_pp3_f32(cfg, k, 1, s);      // 7x7 window on the single-phase kernel
+            case V2V_TILE_FAMILY_T2:     return bf ? launch_t2_bf16(cfg, k, s) : launch_t2_f32(cfg, k, s);
+            case V2V_TILE_FAMILY_S2:     return bf ? launch_s2_bf16(cfg, k, s) : launch_s2_f32(cfg, k, s);
+            case V2V_TILE_FAMILY_PP3:    return bf ? launch_pp3_bf16(cfg, k, groups, s) : launch_pp3_f32(cfg, k, groups, s);
+            case V2V_TILE_FAMILY_PP2:    return bf ? launch_pp2_bf16(cfg, k, groups, s) : launch_pp2_f32(cfg, k, groups, s);
+            case V2V_TILE_FAMILY_ROWSUM: return launch_rowsum_bf16(k, s);
+            case V2V_TILE_FAMILY_C8:     return bf ? launch_c8_bf16(k, s) : launch_c8_f32(k, s);
+            case V2V_TILE_FAMILY_HEAD:   return bf ? launch_head_bf16(k, s) : launch_head_f32(k, s);
+            case V2V_TILE_FAMILY_PP:     return bf ? launch_pp_bf16(cfg, k, s) : launch_pp_f32(cfg, k, s);
+            case V2V_TILE_FAMILY_PATCH:  return bf ? launch_patch_bf16(cfg, k, s) : launch_patch_f32(cfg, k, s);
+        }
+        return bf ? launch_conv_bf16(cfg, k, ncls, s) : launch_conv_f32(cfg, k, ncls, s);
     }
     const char* name() const override { return "conv_igemm"; }
 };
@@ -469,11 +456,14 @@ static int* status_word() {
 static int build_conv(const v2v_conv_desc* d_in, ConvOp* op, bool launching = true) {
     const v2v_conv_desc* d = d_in;
     if (!d || !d->in || !d->w || !d->out || !d->zero_page) { set_error("conv: null pointer"); return V2V_EINVAL; }
+    const ConvTile* t = d->tile ? find_conv_tile(d->tile) : nullptr;       // tile 0: chosen below
+    if (d->tile && !t) { set_error("conv: unknown tile config %d", d->tile); return V2V_EINVAL; }
+    const int fam = t ? t->family : V2V_TILE_FAMILY_IGEMM;
     // Persistent single-chunk tiles (140 - 143) on a layer with 64-byte pixels: the PAIRED-X view (include/v2v_hip.h, w_korder 3).  The
     // NHWC tensors [H][W][32] are [H][W/2][64]; the caller packed the 64 -> 64 matrix of that view (engine.PairedXConv) chunk-major.
     v2v_conv_desc dd;
     bool pair_x = false;
-    if (d->tile >= 140 && d->tile <= 143 && d->cin_stride == 32) {
+    if (fam == V2V_TILE_FAMILY_ONE && d->cin_stride == 32) {
         if (d->dtype != V2V_BF16 || d->transposed || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1 || d->cin > 32 || d->cout != 32 ||
             d->cout_stride != 32 || (d->out_mode != V2V_OUT_RAW_F32_NHWC && d->out_mode != V2V_OUT_RAW_ACT_NHWC) || d->w_korder != 3 || (d->W & 1) || d->OW != d->W || d->OH != d->H) {
             set_error("conv: tile configs 140 - 143 on 64-byte pixels (paired-x view) need a bf16 3x3/s1/p1 Conv2d, <= 32 -> exactly 32 channels, "
@@ -485,7 +475,7 @@ static int build_conv(const v2v_conv_desc* d_in, ConvOp* op, bool launching = tr
         dd.cin = 64; dd.cin_stride = 64; dd.cout = 64; dd.cout_stride = 64; dd.w_korder = 1;
         d = &dd;
         pair_x = true;
-    } else if (d->tile == 114 && d->cin_stride == 32) {
+    } else if (fam == V2V_TILE_FAMILY_T2_ONE && d->cin_stride == 32) {
         // ... and the transposed counterpart: ConvTranspose2d <= 32 -> 16 over [H][W][32] as 64 -> 32 over [H][W/2][64], output [2H][2W][16] = [2H][W][32]
         if (d->dtype != V2V_BF16 || !d->transposed || d->KH != 3 || d->KW != 3 || d->stride != 2 || d->pad != 1 || d->cin > 32 || d->cout != 16 ||
             d->cout_stride != 16 || (d->out_mode != V2V_OUT_RAW_F32_NHWC && d->out_mode != V2V_OUT_RAW_ACT_NHWC) || d->w_korder != 3 || (d->W & 1) || d->OW != 2 * d->W || d->OH != 2 * d->H) {
@@ -561,14 +551,14 @@ static int build_conv(const v2v_conv_desc* d_in, ConvOp* op, bool launching = tr
     }
     k.out_mode = d->out_mode; k.act = d->act; k.act_param = d->act_param; k.out_scale = d->out_scale;
     if (d->act_split != 0) {
-        if (d->act_split < 0 || d->act_split >= d->cout || (d->tile != 60 && d->tile != 62) || d->out_mode != V2V_OUT_F32_NCHW) {
+        if (d->act_split < 0 || d->act_split >= d->cout || (fam != V2V_TILE_FAMILY_HEAD && fam != V2V_TILE_FAMILY_ROWSUM) || d->out_mode != V2V_OUT_F32_NCHW) {
             set_error("conv: act_split (merged heads) needs tile 60 / 62, planar fp32 output and 0 < act_split < cout"); return V2V_EINVAL;
         }
         k.act_split = d->act_split; k.act_b = d->act_b; k.act_param_b = d->act_param_b; k.out_scale_b = d->out_scale_b;
     }
     if (d->out_mode == V2V_OUT_NORM_ACT_NHWC) {
         if ((launching && (!d->fin_counter || !d->stats || !d->fin_scale_shift || d->fin_count <= 0)) || d->splitk > 1 || d->transposed ||
-            d->cout != d->cout_stride || !((d->tile >= 80 && d->tile < 88) || (d->tile >= 90 && d->tile <= 93)) || d->cout > 128 * 64) {
+            d->cout != d->cout_stride || !(t && (t->flags & V2V_TILE_FUSED_NORM)) || d->cout > 128 * 64) {
             set_error("conv: fused norm needs tile 80..87 / 90..93, splitk <= 1, cout == cout_stride, stats (tagged granules: rows * cout * 4 zero-initialised floats), fin_counter (V2V_FIN_TAG_WORD + 128 ints), fin_scale_shift, fin_count");
             return V2V_EINVAL;
         }
@@ -593,16 +583,29 @@ static int build_conv(const v2v_conv_desc* d_in, ConvOp* op, bool launching = tr
     }
     op->ncls = g.ncls;
     op->dtype = d->dtype;
-    op->cfg = d->tile ? d->tile : choose_cfg(Mc, d->cout, g.ncls);
-    if (d->out_mode == V2V_OUT_RAW_ACT_NHWC && (op->cfg == 60 || op->cfg == 61)) {
-        set_error("conv: tile config %d writes fp32 raw only (V2V_OUT_RAW_F32_NHWC)", op->cfg); return V2V_EINVAL;
+    if (!t) t = find_conv_tile(choose_cfg(Mc, d->cout, g.ncls));
+    op->tile = t;
+    if ((t->flags & V2V_TILE_BF16_ONLY) && d->dtype != V2V_BF16) { set_error("conv: tile config %d is bf16 only", t->id); return V2V_EINVAL; }
+    if (d->out_mode == V2V_OUT_RAW_ACT_NHWC && (fam == V2V_TILE_FAMILY_HEAD || fam == V2V_TILE_FAMILY_C8)) {
+        set_error("conv: tile config %d writes fp32 raw only (V2V_OUT_RAW_F32_NHWC)", t->id); return V2V_EINVAL;
     }
-    int tile_bm, tile_bn;
-    if (op->cfg == 61) {
+    // the launch grid: m_tiles pixel tiles x n_tiles channel tiles (x classes, x split-K)
+    const bool t2 = fam == V2V_TILE_FAMILY_T2 || fam == V2V_TILE_FAMILY_T2_ONE;
+    if (fam == V2V_TILE_FAMILY_IGEMM) {
+        k.m_tiles = (int)ceil_div(Mc, t->bm);
+    } else {                                                   // th x tw pixels (transposed stride-2 tiles: input positions (a, b), output pixels (2a + py, 2b + px))
+        k.tiles_h = (int)ceil_div(t2 ? (d->OH + 1) / 2 : d->OH, t->th);
+        k.tiles_w = (int)ceil_div(t2 ? (d->OW + 1) / 2 : d->OW, t->tw);
+        k.m_tiles = d->N * k.tiles_h * k.tiles_w;
+    }
+    const bool head7 = fam == V2V_TILE_FAMILY_HEAD || fam == V2V_TILE_FAMILY_C8 || fam == V2V_TILE_FAMILY_ROWSUM;     // all output channels in one tile
+    k.n_tiles = head7 ? 1 : (int)ceil_div(d->cout, t->bn);
+    const long long in_bytes = (long long)d->N * d->H * d->W * d->cin_stride * (d->dtype == V2V_BF16 ? 2 : 4);    // the patch kernels address the input with 32-bit byte offsets
+    switch (fam) {
+    case V2V_TILE_FAMILY_C8: {
         // conv7x7_c8_kernel: 7x7 / stride 1 / pad 3 Conv2d over pixels of exactly 16 bytes (8 bf16 / 4 fp32 channels), <= 128 output channels
         // Round 6: zero padding of 3 ... 6 (the output grid is then (H + 2 pad - 6) x (W + 2 pad - 6): pad 6 is the "full" convolution the
         // backward-data of a head behind ReflectionPad2d(3) is), and activation-typed NHWC output without activation for that use
-        const int vec = d->dtype == V2V_BF16 ? 8 : 4;
         const bool act_out = d->out_mode == V2V_OUT_ACT_NHWC;
         if (d->transposed || d->KH != 7 || d->KW != 7 || d->stride != 1 || d->pad < 3 || d->pad > 6 || (d->pad != 3 && d->pad_mode != V2V_PAD_ZERO) ||
             d->OH != d->H + 2 * d->pad - 6 || d->OW != d->W + 2 * d->pad - 6 || d->cout > 128 ||
@@ -615,134 +618,91 @@ static int build_conv(const v2v_conv_desc* d_in, ConvOp* op, bool launching = tr
                       "16 bytes, cout <= 128, planar fp32 / raw NHWC output without in-kernel norm finalize, or plain activation-typed NHWC output "
                       "(no activation, whole 16-byte vectors)"); return V2V_EINVAL;
         }
-        k.tiles_h = (int)ceil_div(d->OH, 8);
-        k.tiles_w = (int)ceil_div(d->OW, 32);
-        k.m_tiles = d->N * k.tiles_h * k.tiles_w;
-        k.n_tiles = 1;
-        tile_bm = 256; tile_bn = 4;
-    } else if (op->cfg == 62) {
+        break;
+    }
+    case V2V_TILE_FAMILY_ROWSUM:
         // conv7x7_rowsum_kernel: the generator heads (7x7 / stride 1 / pad 3 Conv2d, <= 4 output channels, planar fp32 + activation), bf16
-        if (d->transposed || d->KH != 7 || d->KW != 7 || d->stride != 1 || d->pad != 3 || d->cout > 4 || d->dtype != V2V_BF16 ||
+        if (d->transposed || d->KH != 7 || d->KW != 7 || d->stride != 1 || d->pad != 3 || d->cout > 4 ||
             d->cin_stride % 32 != 0 || d->w_korder != 0 || d->splitk > 1 || d->fin_counter || d->stats || d->out_mode != V2V_OUT_F32_NCHW ||
-            (long long)d->N * d->H * d->W * d->cin_stride * 2 >= (1ll << 32)) {
+            in_bytes >= (1ll << 32)) {
             set_error("conv: tile config 62 (7x7 heads as row GEMM + shifted sum) needs a bf16 7x7/s1/p3 Conv2d with cout <= 4, cin_stride %% 32 == 0, "
                       "planar fp32 output, no statistics"); return V2V_EINVAL;
         }
-        k.tiles_h = (int)ceil_div(d->OH, 10);
-        k.tiles_w = (int)ceil_div(d->OW, 32);
-        k.m_tiles = d->N * k.tiles_h * k.tiles_w;
-        k.n_tiles = 1;
-        tile_bm = 320; tile_bn = 4;
-    } else if (op->cfg == 60) {
+        break;
+    case V2V_TILE_FAMILY_HEAD:
         // conv7x7_head_kernel: 7x7 / stride 1 / pad 3 Conv2d with <= 16 output channels written planar fp32
         if (d->transposed || d->KH != 7 || d->KW != 7 || d->stride != 1 || d->pad != 3 || d->cout > 32 ||
             d->cin_stride % (bke_of(d->dtype) / 2) != 0 || d->w_korder != 0 || d->splitk > 1 || d->fin_counter ||
             !(d->out_mode == V2V_OUT_F32_NCHW || d->out_mode == V2V_OUT_RAW_F32_NHWC) ||
-            (d->stats && d->out_mode != V2V_OUT_RAW_F32_NHWC) ||
-            (long long)d->N * d->H * d->W * d->cin_stride * (d->dtype == V2V_BF16 ? 2 : 4) >= (1ll << 32)) {
+            (d->stats && d->out_mode != V2V_OUT_RAW_F32_NHWC) || in_bytes >= (1ll << 32)) {
             set_error("conv: tile config 60 (7x7, cout <= 32) needs a 7x7/s1/p3 Conv2d, cin_stride %% %d == 0 (whole 64-byte half chunks), planar fp32 or raw "
                       "NHWC output without in-kernel norm finalize", bke_of(d->dtype) / 2); return V2V_EINVAL;
         }
-        k.tiles_h = (int)ceil_div(d->OH, 8);
-        k.tiles_w = (int)ceil_div(d->OW, 32);
-        k.m_tiles = d->N * k.tiles_h * k.tiles_w;
-        k.n_tiles = 1;
-        tile_bm = 256; tile_bn = 4;
-    } else if (op->cfg >= 120 && op->cfg < 130) {
-        // conv3x3_pp3_body with a 7x7 window (tile 120; staged for round 5): dense 7x7 / stride 1 / pad 3 Conv2d whose channel
-        // stride is a whole number of 128-byte chunks, weights channel-chunk major (korder 1), bf16
-        const PatchCfg* pc = find_pp3_cfg(op->cfg);
-        if (!pc) { set_error("conv: unknown tile config %d", op->cfg); return V2V_EINVAL; }
-        if (d->transposed || d->KH != 7 || d->KW != 7 || d->stride != 1 || d->pad != 3 || d->dtype != V2V_BF16 ||
+        break;
+    case V2V_TILE_FAMILY_S7:
+        // conv3x3_pp3_body with a 7x7 window: dense 7x7 / stride 1 / pad 3 Conv2d whose channel stride is a whole number of 128-byte
+        // chunks, weights channel-chunk major (korder 1), bf16
+        if (d->transposed || d->KH != 7 || d->KW != 7 || d->stride != 1 || d->pad != 3 ||
             d->cin_stride % bke_of(d->dtype) != 0 || d->w_korder != 1 || d->out_mode == V2V_OUT_NORM_ACT_NHWC ||
-            (d->pad_mode == V2V_PAD_REFLECT && (d->H <= 3 || d->W <= 3)) ||
-            (long long)d->N * d->H * d->W * d->cin_stride * 2 >= (1ll << 32)) {
+            (d->pad_mode == V2V_PAD_REFLECT && (d->H <= 3 || d->W <= 3)) || in_bytes >= (1ll << 32)) {
             set_error("conv: tile config %d needs a bf16 7x7/s1/p3 Conv2d, cin_stride %% %d == 0, korder-1 weights, no fused norm",
-                      op->cfg, bke_of(d->dtype)); return V2V_EINVAL;
+                      t->id, bke_of(d->dtype)); return V2V_EINVAL;
         }
-        k.tiles_h = (int)ceil_div(d->OH, pc->TH);
-        k.tiles_w = (int)ceil_div(d->OW, pc->TW);
-        k.m_tiles = d->N * k.tiles_h * k.tiles_w;
-        k.n_tiles = (int)ceil_div(d->cout, pc->BN);
-        tile_bm = pc->TH * pc->TW; tile_bn = pc->BN;
-    } else if (op->cfg >= 110 && op->cfg < 120) {
+        break;
+    case V2V_TILE_FAMILY_T2: case V2V_TILE_FAMILY_T2_ONE:
         // conv3x3_t2_kernel: ConvTranspose2d(3x3, stride 2, padding 1), all four output-parity classes per workgroup, full-tap (korder 2) weights
-        const PatchCfg* pc = find_t2_cfg(op->cfg);
-        if (!pc) { set_error("conv: unknown tile config %d", op->cfg); return V2V_EINVAL; }
         if (!d->transposed || d->KH != 3 || d->KW != 3 || d->stride != 2 || d->pad != 1 ||
             d->cin_stride % bke_of(d->dtype) != 0 || d->w_korder != 2 || d->splitk > 1 || d->out_mode == V2V_OUT_NORM_ACT_NHWC ||
-            (long long)d->N * d->H * d->W * d->cin_stride * (d->dtype == V2V_BF16 ? 2 : 4) >= (1ll << 32)) {
+            in_bytes >= (1ll << 32)) {
             set_error("conv: transposed stride-2 patch tile config %d needs a ConvTranspose2d(3x3, s2, p1), cin_stride %% %d == 0, korder-2 weights, no split-K",
-                      op->cfg, bke_of(d->dtype)); return V2V_EINVAL;
+                      t->id, bke_of(d->dtype)); return V2V_EINVAL;
         }
-        k.tiles_h = (int)ceil_div((d->OH + 1) / 2, pc->TH);    // tiles of input positions (a, b): output pixels (2a + py, 2b + px)
-        k.tiles_w = (int)ceil_div((d->OW + 1) / 2, pc->TW);
-        k.m_tiles = d->N * k.tiles_h * k.tiles_w;
-        k.n_tiles = (int)ceil_div(d->cout, pc->BN);
-        if (op->cfg == 114 && (d->dtype != V2V_BF16 || d->cin_stride != 64 || d->cout > pc->BN || (d->cout & 3) || (d->cout_stride & 3) || ((unsigned long long)d->out & 15ull) ||
-                               (d->out_mode != V2V_OUT_RAW_F32_NHWC && d->out_mode != V2V_OUT_RAW_ACT_NHWC) || d->fin_workspace != nullptr || d->H % pc->TH != 0 || d->W % pc->TW != 0 ||
+        if (fam == V2V_TILE_FAMILY_T2_ONE && (d->cin_stride != 64 || d->cout > t->bn || (d->cout & 3) || (d->cout_stride & 3) || ((unsigned long long)d->out & 15ull) ||
+                               (d->out_mode != V2V_OUT_RAW_F32_NHWC && d->out_mode != V2V_OUT_RAW_ACT_NHWC) || d->fin_workspace != nullptr || d->H % t->th != 0 || d->W % t->tw != 0 ||
                                d->OH != 2 * d->H || d->OW != 2 * d->W)) {
             // conv3x3_one_kernel.h, conv3x3_t2_one_kernel: ONE output mode (raw fp32 NHWC + one statistics row per workgroup), full tiles only
-            set_error("conv: tile config 114 (persistent transposed stride-2 tile) needs bf16, cin_stride 64, cout <= %d and %% 4 == 0, raw fp32 NHWC output (16-byte aligned "
-                      "rows), no two-level finalize workspace, H %% %d == 0, W %% %d == 0, OH = 2 H, OW = 2 W", pc->BN, pc->TH, pc->TW);
+            set_error("conv: tile config %d (persistent transposed stride-2 tile) needs bf16, cin_stride 64, cout <= %d and %% 4 == 0, raw fp32 NHWC output (16-byte aligned "
+                      "rows), no two-level finalize workspace, H %% %d == 0, W %% %d == 0, OH = 2 H, OW = 2 W", t->id, t->bn, t->th, t->tw);
             return V2V_EINVAL;
         }
         k.woff[0] = 0; k.wrow[0] = 9 * d->cin_stride;          // the single full-tap matrix
-        k.fin_rows = op->cfg == 114 ? 0 : 4 * k.m_tiles;       // every workgroup publishes one statistics row per class (114: one per workgroup, all classes)
-        tile_bm = pc->TH * pc->TW; tile_bn = pc->BN;
-    } else if (op->cfg >= 100 && op->cfg < 110) {
+        k.fin_rows = (t->flags & V2V_TILE_PERSISTENT) ? 0 : 4 * k.m_tiles;      // every workgroup publishes one statistics row per class (persistent: one per workgroup, all classes)
+        break;
+    case V2V_TILE_FAMILY_S2:
         // conv3x3_s2_kernel: 3x3 / stride 2 / pad 1 (zero) Conv2d, channel stride a multiple of the 128-byte chunk, korder-1 weights
-        const PatchCfg* pc = find_s2_cfg(op->cfg);
-        if (!pc) { set_error("conv: unknown tile config %d", op->cfg); return V2V_EINVAL; }
         if (d->transposed || d->KH != 3 || d->KW != 3 || d->stride != 2 || d->pad != 1 || d->pad_mode != V2V_PAD_ZERO ||
             d->cin_stride % bke_of(d->dtype) != 0 || d->w_korder != 1 || d->splitk > 1 || d->out_mode == V2V_OUT_NORM_ACT_NHWC ||
-            (long long)d->N * d->H * d->W * d->cin_stride * (d->dtype == V2V_BF16 ? 2 : 4) >= (1ll << 32)) {
+            in_bytes >= (1ll << 32)) {
             set_error("conv: stride-2 patch tile config %d needs a 3x3/s2/p1 zero-padded Conv2d, cin_stride %% %d == 0, korder-1 weights, no split-K",
-                      op->cfg, bke_of(d->dtype)); return V2V_EINVAL;
+                      t->id, bke_of(d->dtype)); return V2V_EINVAL;
         }
-        k.tiles_h = (int)ceil_div(d->OH, pc->TH);
-        k.tiles_w = (int)ceil_div(d->OW, pc->TW);
-        k.m_tiles = d->N * k.tiles_h * k.tiles_w;
-        k.n_tiles = (int)ceil_div(d->cout, pc->BN);
-        tile_bm = pc->TH * pc->TW; tile_bn = pc->BN;
-    } else if (op->cfg >= 32) {
-        // conv3x3_patch_kernel: 3x3 / stride 1 / pad 1 Conv2d, channel stride a multiple of the 128-byte chunk,
+        break;
+    case V2V_TILE_FAMILY_PATCH: case V2V_TILE_FAMILY_PP: case V2V_TILE_FAMILY_PP2: case V2V_TILE_FAMILY_PP3: case V2V_TILE_FAMILY_ONE: {
+        // conv3x3_patch_kernel and its successors: 3x3 / stride 1 / pad 1 Conv2d, channel stride a multiple of the 128-byte chunk,
         // weights packed channel-chunk outer (korder 1)
-        const PatchCfg* pc = op->cfg >= 80 ? find_pp3_cfg(op->cfg) : op->cfg >= 70 ? find_pp2_cfg(op->cfg) : op->cfg >= 50 ? find_pp_cfg(op->cfg) : find_patch_cfg(op->cfg);
-        if (!pc) { set_error("conv: unknown tile config %d", op->cfg); return V2V_EINVAL; }
-        const bool pad2_ok = d->pad == 2 && op->cfg >= 80 && op->cfg <= 93 && d->pad_mode == V2V_PAD_ZERO && d->out_mode != V2V_OUT_NORM_ACT_NHWC;   // single-phase tiles: "full" 3x3 convolution (backward-data behind a ReflectionPad2d)
+        const bool pad2_ok = d->pad == 2 && (t->flags & V2V_TILE_PAD2) && d->pad_mode == V2V_PAD_ZERO && d->out_mode != V2V_OUT_NORM_ACT_NHWC;   // single-phase tiles: "full" 3x3 convolution (backward-data behind a ReflectionPad2d)
         if (d->transposed || d->KH != 3 || d->KW != 3 || d->stride != 1 || (d->pad != 1 && !pad2_ok) ||
-            d->cin_stride % bke_of(d->dtype) != 0 || d->w_korder != 1 ||
-            (long long)d->N * d->H * d->W * d->cin_stride * (d->dtype == V2V_BF16 ? 2 : 4) >= (1ll << 32)) {
+            d->cin_stride % bke_of(d->dtype) != 0 || d->w_korder != 1 || in_bytes >= (1ll << 32)) {
             set_error("conv: patch tile config %d needs a 3x3/s1/p1 Conv2d, cin_stride %% %d == 0 and korder-1 weights",
-                      op->cfg, bke_of(d->dtype)); return V2V_EINVAL;
+                      t->id, bke_of(d->dtype)); return V2V_EINVAL;
         }
-        if ((op->cfg >= 140 && op->cfg <= 143) && ((op->cfg >= 142 && d->cout != pc->BN) || d->cout > pc->BN || (d->cout & 3) || (d->cout_stride & 3) || ((unsigned long long)d->out & 15ull) ||
-                               (d->out_mode != V2V_OUT_RAW_F32_NHWC && d->out_mode != V2V_OUT_RAW_ACT_NHWC) || d->fin_workspace != nullptr || d->OH % pc->TH != 0 || d->OW % pc->TW != 0)) {
+        if (fam == V2V_TILE_FAMILY_ONE && (((t->flags & V2V_TILE_EXACT_BN) && d->cout != t->bn) || d->cout > t->bn || (d->cout & 3) || (d->cout_stride & 3) || ((unsigned long long)d->out & 15ull) ||
+                               (d->out_mode != V2V_OUT_RAW_F32_NHWC && d->out_mode != V2V_OUT_RAW_ACT_NHWC) || d->fin_workspace != nullptr || d->OH % t->th != 0 || d->OW % t->tw != 0)) {
             // conv3x3_one_kernel.h: ONE output mode (raw fp32 NHWC + one statistics row per workgroup, single-level in-kernel finalize), full tiles only
-            set_error("conv: tile configs 140 - 143 (persistent, weights resident) need cout <= %d (142 / 143: exactly) and %% 4 == 0, raw fp32 NHWC output (16-byte aligned rows), "
-                      "no two-level finalize workspace, OH %% %d == 0 and OW %% %d == 0", pc->BN, pc->TH, pc->TW);
+            set_error("conv: tile configs 140 - 143 (persistent, weights resident) need cout <= %d (143: exactly) and %% 4 == 0, raw fp32 NHWC output (16-byte aligned rows), "
+                      "no two-level finalize workspace, OH %% %d == 0 and OW %% %d == 0", t->bn, t->th, t->tw);
             return V2V_EINVAL;
         }
-        if ((op->cfg == 94 || op->cfg == 95 || op->cfg == 96 || (op->cfg >= 140 && op->cfg <= 143)) && (d->dtype != V2V_BF16 || d->cin_stride != bke_of(d->dtype) || d->splitk > 1 ||
-                                                 d->out_mode == V2V_OUT_NORM_ACT_NHWC)) {
-            set_error("conv: tile config %d is a single-chunk tile: bf16, cin_stride exactly %d, no split-K, no fused norm", op->cfg, bke_of(d->dtype));
+        if ((t->flags & V2V_TILE_SINGLE_CHUNK) && (d->cin_stride != bke_of(d->dtype) || d->splitk > 1 || d->out_mode == V2V_OUT_NORM_ACT_NHWC)) {
+            set_error("conv: tile config %d is a single-chunk tile: bf16, cin_stride exactly %d, no split-K, no fused norm", t->id, bke_of(d->dtype));
             return V2V_EINVAL;
         }
-        k.tiles_h = (int)ceil_div(d->OH, pc->TH);
-        k.tiles_w = (int)ceil_div(d->OW, pc->TW);
-        k.m_tiles = d->N * k.tiles_h * k.tiles_w;
-        k.n_tiles = (int)ceil_div(d->cout, pc->BN);
-        tile_bm = pc->TH * pc->TW; tile_bn = pc->BN;
-    } else {
-        if (d->w_korder != 0) { set_error("conv: tile config %d reads tap-major (korder 0) weights", op->cfg); return V2V_EINVAL; }
-        const TileCfg* c = find_cfg(op->cfg);
-        if (!c) { set_error("conv: unknown tile config %d", op->cfg); return V2V_EINVAL; }
-        k.m_tiles = (int)ceil_div(Mc, c->BM);
-        k.n_tiles = (int)ceil_div(d->cout, c->BN);
-        tile_bm = c->BM; tile_bn = c->BN;
+        break;
     }
-    if (op->cfg >= 32 && k.tiles_h > 0 && k.tiles_w > 0 && k.m_tiles > 0) {   // patch kernels: tile-index divisions by multiplication (ConvKArgs.idx_m)
+    default:                                                   // implicit GEMM
+        if (d->w_korder != 0) { set_error("conv: tile config %d reads tap-major (korder 0) weights", t->id); return V2V_EINVAL; }
+    }
+    if (fam != V2V_TILE_FAMILY_IGEMM && k.tiles_h > 0 && k.tiles_w > 0 && k.m_tiles > 0) {   // patch kernels: tile-index divisions by multiplication (ConvKArgs.idx_m)
         const uint32_t dv[3] = {(uint32_t)k.m_tiles, (uint32_t)(k.tiles_h * k.tiles_w), (uint32_t)k.tiles_w};
         for (int i = 0; i < 3; ++i) {
             uint32_t m = 0; int32_t l = 0;
@@ -754,12 +714,12 @@ static int build_conv(const v2v_conv_desc* d_in, ConvOp* op, bool launching = tr
     k.splitk = d->splitk > 1 ? d->splitk : 1;
     int nk_min = k.kpad[0] / bke_of(d->dtype);
     for (int cc = 1; cc < g.ncls; ++cc) nk_min = std::min(nk_min, k.kpad[cc] / bke_of(d->dtype));
-    if (op->cfg >= 32) nk_min = 2 * (d->cin_stride / bke_of(d->dtype));     // slices are whole channel chunks (>= 1 each)
+    if (fam != V2V_TILE_FAMILY_IGEMM) nk_min = 2 * (d->cin_stride / bke_of(d->dtype));     // slices are whole channel chunks (>= 1 each)
     if (k.splitk > 1 && (k.splitk > 16 || nk_min / k.splitk < 2)) {
         set_error("conv: splitk %d needs >= 2 K chunks per slice (layer has %d)", k.splitk, nk_min); return V2V_EINVAL;
     }
     op->sk_tickets = g.ncls * k.m_tiles * k.n_tiles;
-    op->slab_bytes = k.splitk > 1 ? (long long)op->sk_tickets * k.splitk * tile_bm * tile_bn * 4 : 0;
+    op->slab_bytes = k.splitk > 1 ? (long long)op->sk_tickets * k.splitk * t->bm * t->bn * 4 : 0;
     if (k.splitk > 1) {
         if (launching && (!d->slabs || !d->sk_counter)) { set_error("conv: splitk needs slabs and sk_counter"); return V2V_EINVAL; }
         k.slabs = (float*)d->slabs; k.sk_counter = d->sk_counter;
@@ -779,7 +739,7 @@ static int build_conv(const v2v_conv_desc* d_in, ConvOp* op, bool launching = tr
         static const int rev = [] { const char* e = getenv("V2V_CLS_ORDER"); return (e && e[0] == '0') ? 0 : 1; }();
         k.cls_rev = rev;
     }
-    k.pf_dist = (d->prefetch > 0 && (conv_cfg_has_helper(op->cfg) || (op->cfg >= 32 && op->cfg <= 37))) ? d->prefetch : 0;
+    k.pf_dist = (d->prefetch > 0 && (t->flags & V2V_TILE_HELPER)) ? d->prefetch : 0;
     {
         static const int ep_fast = [] { const char* e = getenv("V2V_EPILOGUE_FAST"); return (e && e[0] == '0') ? 0 : 1; }();
         k.ep_slow = ep_fast ? 0 : 1;
@@ -862,7 +822,7 @@ extern "C" int v2v_conv_debug_clocks(void* device_buffer) {
 extern "C" int v2v_conv_stats_rows(const v2v_conv_desc* d) {
     ConvOp op;
     if (build_conv(d, &op, false) != 0) return V2V_EINVAL;
-    if (op.cfg >= 140 || op.cfg == 114) return one_grid(op.k.m_tiles * op.k.n_tiles, device_cus());     // persistent tiles: one row per workgroup
+    if (op.tile->flags & V2V_TILE_PERSISTENT) return one_grid(op.k.m_tiles * op.k.n_tiles, device_cus());     // persistent tiles: one row per workgroup
     return op.ncls * op.k.m_tiles;
 }
 
@@ -873,10 +833,19 @@ extern "C" int64_t v2v_conv_splitk_workspace(const v2v_conv_desc* d, int32_t* ti
     return op.slab_bytes;
 }
 
+extern "C" int v2v_conv_tile_count(void) { return kNumConvTiles; }
+
+extern "C" int v2v_conv_tile_info(int32_t index, struct v2v_conv_tile_info* out) {
+    if (index < 0 || index >= kNumConvTiles || !out) { set_error("conv tile info: index %d outside [0, %d)", index, kNumConvTiles); return V2V_EINVAL; }
+    const ConvTile& t = kConvTiles[index];
+    *out = {t.id, t.family, t.bm, t.bn, t.th, t.tw, t.korder, t.flags};
+    return 0;
+}
+
 extern "C" int v2v_conv_tile_config(const v2v_conv_desc* d) {
     ConvOp op;
     if (build_conv(d, &op, false) != 0) return V2V_EINVAL;
-    return op.cfg;
+    return op.tile->id;
 }
 
 // Fused norm: the spin barrier needs every workgroup of the launch on the chip at once (one workgroup per CU at these
@@ -919,8 +888,8 @@ extern "C" int v2v_conv2d_pair(const v2v_conv_desc* a, const v2v_conv_desc* b, v
     int rc = build_conv(a, op.get());
     if (rc == 0) rc = build_conv(b, &ob);
     if (rc != 0) return rc;
-    if (op->cfg < 70 || op->cfg >= 94 || ob.cfg != op->cfg) {
-        set_error("conv pair: both members need the same grouped-launch tile config (70..93), got %d / %d", op->cfg, ob.cfg);
+    if (!(op->tile->flags & V2V_TILE_GROUPED) || ob.tile != op->tile) {
+        set_error("conv pair: both members need the same grouped-launch tile config (70..93), got %d / %d", op->tile->id, ob.tile->id);
         return V2V_EINVAL;
     }
     const bool same =

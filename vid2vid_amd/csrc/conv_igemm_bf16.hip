@@ -8,7 +8,6 @@
 #include "conv7x7_head_kernel.h"
 namespace v2v {
 int launch_conv_bf16(int cfg, const ConvKArgs& k, int ncls, hipStream_t s) { return launch_typed<bf16_t>(cfg, k, ncls, s); }
-bool conv_cfg_has_helper(int cfg) { return cfg_has_helper_impl(cfg); }
 int launch_patch_bf16(int cfg, const ConvKArgs& k, hipStream_t s) { return launch_patch_typed<bf16_t>(cfg, k, s); }
 int launch_pp_bf16(int cfg, const ConvKArgs& k, hipStream_t s) { return launch_pp_typed<bf16_t>(cfg, k, s); }
 int launch_pp2_bf16(int cfg, const ConvKArgs& k, int groups, hipStream_t s) { return launch_pp2_typed<bf16_t>(cfg, k, groups, s); }

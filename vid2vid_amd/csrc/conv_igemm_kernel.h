@@ -2,6 +2,7 @@
 // per-dtype instantiation units conv_igemm_bf16.hip / conv_igemm_f32.hip and by the host side.
 #pragma once
 #include "v2v_internal.h"
+#include "conv_tiles.h"
 
 namespace v2v {
 
@@ -1212,38 +1213,32 @@ static int launch_cfg(const ConvKArgs& k, int ncls, hipStream_t s) {
 template <typename T>
 static inline int launch_typed(int cfg, const ConvKArgs& k, int ncls, hipStream_t s) {
     switch (cfg) {
-        case 1: return launch_cfg<T, 128, 128, 2, 2, 3, false>(k, ncls, s);   //  96 KiB LDS
-        case 2: return k.pf_dist > 0 ? launch_cfg<T, 128, 64, 2, 2, 4, true>(k, ncls, s) : launch_cfg<T, 128, 64, 2, 2, 4, false>(k, ncls, s);    //  96 KiB
-        case 3: return k.pf_dist > 0 ? launch_cfg<T, 64, 64, 2, 2, 4, true>(k, ncls, s) : launch_cfg<T, 64, 64, 2, 2, 4, false>(k, ncls, s);     //  64 KiB (2 workgroups / CU)
-        case 4: return launch_cfg<T, 128, 32, 4, 1, 4, false>(k, ncls, s);    //  80 KiB (2 / CU)
-        case 5: return k.pf_dist > 0 ? launch_cfg<T, 64, 128, 2, 2, 4, true>(k, ncls, s) : launch_cfg<T, 64, 128, 2, 2, 4, false>(k, ncls, s);    //  96 KiB
-        case 6: return launch_cfg<T, 256, 64, 4, 1, 3, false>(k, ncls, s);    // 120 KiB
-        case 7: return k.pf_dist > 0 ? launch_cfg<T, 128, 64, 2, 2, 6, true>(k, ncls, s) : launch_cfg<T, 128, 64, 2, 2, 6, false>(k, ncls, s);    // 144 KiB
-        case 8: return launch_cfg<T, 128, 128, 2, 2, 4, false>(k, ncls, s);   // 128 KiB
-        case 9: return k.pf_dist > 0 ? launch_cfg<T, 64, 64, 2, 2, 3, true>(k, ncls, s) : launch_cfg<T, 64, 64, 2, 2, 3, false>(k, ncls, s);     //  48 KiB (3 workgroups / CU)
-        case 10: return launch_cfg<T, 64, 64, 2, 2, 2, false>(k, ncls, s);    //  32 KiB (5 / CU)
-        case 11: return k.pf_dist > 0 ? launch_cfg<T, 128, 64, 2, 2, 2, true>(k, ncls, s) : launch_cfg<T, 128, 64, 2, 2, 2, false>(k, ncls, s);   //  48 KiB (3 / CU)
-        case 12: return k.pf_dist > 0 ? launch_cfg<T, 64, 128, 2, 2, 3, true>(k, ncls, s) : launch_cfg<T, 64, 128, 2, 2, 3, false>(k, ncls, s);   //  72 KiB (2 / CU)
-        case 13: return k.pf_dist > 0 ? launch_cfg<T, 128, 64, 4, 2, 3, true>(k, ncls, s) : launch_cfg<T, 128, 64, 4, 2, 3, false>(k, ncls, s);   //  72 KiB, 8 waves (2 / CU)
-        case 14: return launch_cfg<T, 128, 128, 4, 2, 2, false>(k, ncls, s);  //  64 KiB, 8 waves (2 / CU)
-        case 15: return launch_cfg<T, 128, 128, 2, 4, 3, false>(k, ncls, s);  //  96 KiB, 8 waves
-        case 16: return launch_cfg<T, 256, 64, 4, 2, 2, false>(k, ncls, s);   //  80 KiB, 8 waves
-        case 17: return k.pf_dist > 0 ? launch_cfg<T, 64, 128, 2, 4, 3, true>(k, ncls, s) : launch_cfg<T, 64, 128, 2, 4, 3, false>(k, ncls, s);   //  72 KiB, 8 waves (2 / CU)
-        case 18: return launch_cfg<T, 256, 128, 4, 2, 3, false>(k, ncls, s);  // 144 KiB, 8 waves, wave tile 64x64
-        case 19: return launch_cfg<T, 256, 128, 2, 2, 3, false>(k, ncls, s);  // 144 KiB, 4 waves, wave tile 128x64
-        case 20: return launch_cfg<T, 128, 256, 2, 4, 3, false>(k, ncls, s);  // 144 KiB, 8 waves, wave tile 64x64
-        case 21: return launch_cfg<T, 128, 128, 2, 2, 2, false>(k, ncls, s);  //  64 KiB, 4 waves, wave tile 64x64 (2 / CU)
-        case 22: return launch_cfg<T, 256, 128, 4, 2, 2, false>(k, ncls, s);  //  96 KiB, 8 waves, wave tile 64x64
-        case 23: return launch_cfg<T, 128, 256, 2, 2, 3, false>(k, ncls, s);  // 144 KiB, 4 waves, wave tile 64x128
+        case 1: return launch_cfg<T, V2V_TILE_BMBN(1), 2, 2, 3, false>(k, ncls, s);   //  96 KiB LDS
+        case 2: return k.pf_dist > 0 ? launch_cfg<T, V2V_TILE_BMBN(2), 2, 2, 4, true>(k, ncls, s) : launch_cfg<T, V2V_TILE_BMBN(2), 2, 2, 4, false>(k, ncls, s);    //  96 KiB
+        case 3: return k.pf_dist > 0 ? launch_cfg<T, V2V_TILE_BMBN(3), 2, 2, 4, true>(k, ncls, s) : launch_cfg<T, V2V_TILE_BMBN(3), 2, 2, 4, false>(k, ncls, s);     //  64 KiB (2 workgroups / CU)
+        case 4: return launch_cfg<T, V2V_TILE_BMBN(4), 4, 1, 4, false>(k, ncls, s);    //  80 KiB (2 / CU)
+        case 5: return k.pf_dist > 0 ? launch_cfg<T, V2V_TILE_BMBN(5), 2, 2, 4, true>(k, ncls, s) : launch_cfg<T, V2V_TILE_BMBN(5), 2, 2, 4, false>(k, ncls, s);    //  96 KiB
+        case 6: return launch_cfg<T, V2V_TILE_BMBN(6), 4, 1, 3, false>(k, ncls, s);    // 120 KiB
+        case 7: return k.pf_dist > 0 ? launch_cfg<T, V2V_TILE_BMBN(7), 2, 2, 6, true>(k, ncls, s) : launch_cfg<T, V2V_TILE_BMBN(7), 2, 2, 6, false>(k, ncls, s);    // 144 KiB
+        case 8: return launch_cfg<T, V2V_TILE_BMBN(8), 2, 2, 4, false>(k, ncls, s);   // 128 KiB
+        case 9: return k.pf_dist > 0 ? launch_cfg<T, V2V_TILE_BMBN(9), 2, 2, 3, true>(k, ncls, s) : launch_cfg<T, V2V_TILE_BMBN(9), 2, 2, 3, false>(k, ncls, s);     //  48 KiB (3 workgroups / CU)
+        case 10: return launch_cfg<T, V2V_TILE_BMBN(10), 2, 2, 2, false>(k, ncls, s);    //  32 KiB (5 / CU)
+        case 11: return k.pf_dist > 0 ? launch_cfg<T, V2V_TILE_BMBN(11), 2, 2, 2, true>(k, ncls, s) : launch_cfg<T, V2V_TILE_BMBN(11), 2, 2, 2, false>(k, ncls, s);   //  48 KiB (3 / CU)
+        case 12: return k.pf_dist > 0 ? launch_cfg<T, V2V_TILE_BMBN(12), 2, 2, 3, true>(k, ncls, s) : launch_cfg<T, V2V_TILE_BMBN(12), 2, 2, 3, false>(k, ncls, s);   //  72 KiB (2 / CU)
+        case 13: return k.pf_dist > 0 ? launch_cfg<T, V2V_TILE_BMBN(13), 4, 2, 3, true>(k, ncls, s) : launch_cfg<T, V2V_TILE_BMBN(13), 4, 2, 3, false>(k, ncls, s);   //  72 KiB, 8 waves (2 / CU)
+        case 14: return launch_cfg<T, V2V_TILE_BMBN(14), 4, 2, 2, false>(k, ncls, s);  //  64 KiB, 8 waves (2 / CU)
+        case 15: return launch_cfg<T, V2V_TILE_BMBN(15), 2, 4, 3, false>(k, ncls, s);  //  96 KiB, 8 waves
+        case 16: return launch_cfg<T, V2V_TILE_BMBN(16), 4, 2, 2, false>(k, ncls, s);   //  80 KiB, 8 waves
+        case 17: return k.pf_dist > 0 ? launch_cfg<T, V2V_TILE_BMBN(17), 2, 4, 3, true>(k, ncls, s) : launch_cfg<T, V2V_TILE_BMBN(17), 2, 4, 3, false>(k, ncls, s);   //  72 KiB, 8 waves (2 / CU)
+        case 18: return launch_cfg<T, V2V_TILE_BMBN(18), 4, 2, 3, false>(k, ncls, s);  // 144 KiB, 8 waves, wave tile 64x64
+        case 19: return launch_cfg<T, V2V_TILE_BMBN(19), 2, 2, 3, false>(k, ncls, s);  // 144 KiB, 4 waves, wave tile 128x64
+        case 20: return launch_cfg<T, V2V_TILE_BMBN(20), 2, 4, 3, false>(k, ncls, s);  // 144 KiB, 8 waves, wave tile 64x64
+        case 21: return launch_cfg<T, V2V_TILE_BMBN(21), 2, 2, 2, false>(k, ncls, s);  //  64 KiB, 4 waves, wave tile 64x64 (2 / CU)
+        case 22: return launch_cfg<T, V2V_TILE_BMBN(22), 4, 2, 2, false>(k, ncls, s);  //  96 KiB, 8 waves, wave tile 64x64
+        case 23: return launch_cfg<T, V2V_TILE_BMBN(23), 2, 2, 3, false>(k, ncls, s);  // 144 KiB, 4 waves, wave tile 64x128
     }
     set_error("conv: unknown tile config %d", cfg);
     return V2V_EINVAL;
-}
-
-
-static inline bool cfg_has_helper_impl(int cfg) {
-    switch (cfg) { case 2: case 3: case 5: case 7: case 9: case 11: case 12: case 13: case 17: return true; }
-    return false;
 }
 
 }  // namespace v2v

@@ -458,66 +458,54 @@ class Plan:
             pass
 
 
-# tile config id -> (BM, BN, has a prefetch-helper instance)   (csrc/conv_igemm_kernel.h launch_typed)
-TILE_CFGS = {1: (128, 128, False), 2: (128, 64, True), 3: (64, 64, True), 4: (128, 32, False), 5: (64, 128, True),
-             6: (256, 64, False), 7: (128, 64, True), 8: (128, 128, False), 9: (64, 64, True), 10: (64, 64, False),
-             11: (128, 64, True), 12: (64, 128, True), 13: (128, 64, True), 14: (128, 128, False),
-             15: (128, 128, False), 16: (256, 64, False), 17: (64, 128, True), 18: (256, 128, False),
-             19: (256, 128, False), 20: (128, 256, False), 21: (128, 128, False), 22: (256, 128, False),
-             23: (128, 256, False)}
-# LDS-resident-patch 3x3 kernel (csrc/conv3x3_patch_kernel.h): id -> (TH, TW, BN); weights in K order 1
-PATCH_CFGS = {32: (2, 64, 64), 33: (4, 64, 64), 34: (2, 64, 128), 35: (4, 32, 64), 36: (8, 32, 64), 37: (4, 32, 128),
-              40: (2, 64, 64), 41: (4, 64, 64), 42: (2, 64, 128), 43: (4, 32, 64), 44: (8, 32, 64), 45: (4, 32, 128),
-              46: (4, 64, 64), 47: (2, 64, 128), 48: (4, 64, 128),   # 40+: dedicated loader waves
-              # ping-pong wave groups (csrc/conv3x3_pp_kernel.h)
-              50: (4, 64, 128), 51: (4, 64, 64), 52: (2, 64, 128), 53: (8, 32, 128), 54: (8, 32, 64), 55: (4, 32, 128),
-              56: (8, 32, 64), 57: (4, 64, 64),
-              # ping-pong, second schedule: LDS-DMA issued between the MFMAs; the only tiles v2v_conv2d_pair accepts
-              # (csrc/conv3x3_pp2_kernel.h)
-              70: (8, 32, 64), 71: (8, 32, 128), 72: (8, 32, 64), 73: (4, 64, 64), 74: (4, 64, 64), 75: (4, 32, 128),
-              # single-phase software-pipelined schedule (csrc/conv3x3_pp3_kernel.h): two fragment register sets, ONE barrier per step
-              80: (8, 32, 64), 81: (8, 32, 128), 82: (8, 32, 64), 83: (4, 64, 64), 84: (4, 32, 128), 85: (4, 64, 128),
-              86: (4, 32, 128), 87: (2, 64, 128),      # 86 / 87: four waves, 64 x 64 wave tiles
-              90: (8, 32, 64), 91: (4, 64, 64),        # 90 / 91: 82 / 83 with K pairs (8 fragment reads per 8 MFMAs)
-              92: (8, 32, 64), 93: (4, 64, 64),        # 92 / 93: K quads (6 reads per 8 MFMAs)
-              94: (8, 32, 64), 95: (4, 64, 64), 96: (4, 32, 64),
-              # (the round-5 experiment tiles 97-99 / 130-132 on tile 90's geometry and 142 -- all bit-identical to the tiles they varied, none
-              #  faster, DESIGN 3.1 -- were removed in round 6)
-              # csrc/conv3x3_one_kernel.h (round 5): PERSISTENT, weights-resident tile for single-chunk layers with <= 64 output channels
-              # (one workgroup per CU walks its tiles; no barrier / DMA / wait inside a tile's 9 steps).  140: bit-identical to tile 94 and
-              # 18-20 % faster (profiles/r05_v2_one_bench.txt, r05_v3_one_bench.txt); 141 (two patch buffers): another 5 % on the 2048-tile
-              # layer, 5-7 % slower on the small ones (profiles/r05_v6_stagger.txt) -- both are offered, the search decides per shape;
-              # 143: 141 with its stores left in flight (experiment, V2V_EXP_TILES=1).   94 / 95: single-chunk layers (64 bf16 input
-              # channels): one patch buffer, 3 weight stages (72 / 80 KiB)
-              140: (8, 32, 64), 141: (8, 32, 64), 143: (8, 32, 64)}
-# stride-2 3x3 convolutions on the plane-resident patch kernel (csrc/conv3x3_s2_kernel.h): id -> (TH, TW, BN) of the OUTPUT tile
-S2_CFGS = {100: (4, 32, 64), 101: (4, 32, 128), 102: (4, 32, 64), 103: (4, 32, 128)}
-# ConvTranspose2d(3x3, stride 2) with all four output-parity classes per workgroup (csrc/conv3x3_t2_kernel.h): id -> (TH, TW, BN), tile of INPUT positions
-T2_CFGS = {110: (4, 32, 64), 111: (4, 32, 128), 112: (8, 32, 64), 113: (4, 32, 64),
-           114: (8, 32, 32)}     # 114: persistent, weights resident, single chunk (64 input channels), <= 32 output channels (csrc/conv3x3_one_kernel.h)
-# dense 7x7 / stride 1 / pad 3 convolutions on the single-phase kernel with a 7x7 window (csrc/conv3x3_pp3_kernel.h, KK = 7): id -> (TH, TW, BN).
-# Round 5: validated on the GPU (tests/test_gpu_kernels.py::test_conv7x7_window_tiles), offered to the tile search unless V2V_S7_PATCH=0
-S7_CFGS = {120: (4, 32, 64), 121: (4, 32, 128)}
-ABLATION_TILES = {78: (8, 32, 128), 79: (8, 32, 64), 88: (8, 32, 128), 89: (8, 32, 64)}     # instrumented copies of 71 / 70 (scripts/pp2_ablate.py); never auto-selected
-PAIR_TILES = (70, 71, 72, 73, 74, 75, 80, 81, 82, 83, 84, 85, 86, 87, 90, 91, 92, 93)
-ONE_TILES = (140, 141, 143)                                     # persistent, weights-resident single-chunk tiles (csrc/conv3x3_one_kernel.h)
-PERSISTENT_TILES = ONE_TILES + (114,)                           # ... and the transposed stride-2 one: ONE statistics row per workgroup, finalize in the launch at any size
+# What a tile id is -- kernel family, geometry, weight packing, capabilities -- is written down once, in the library's tile table
+# (csrc/conv_tiles.h, read through v2v_conv_tile_info); the names below are views of it.
+_TILES = L.conv_tiles()
+
+
+def _geom(pick):
+    return {t: (r.th, r.tw, r.bn) for t, r in sorted(_TILES.items()) if pick(r)}
+
+
+def _flag(t, bit):
+    """Flag `bit` of tile id t; False for 0 (auto) and ids the library does not know (it refuses them)."""
+    return t in _TILES and bool(_TILES[t].flags & bit)
+
+
+# implicit-GEMM tiles: id -> (BM, BN, has a prefetch-helper instance)
+TILE_CFGS = {t: (r.bm, r.bn, bool(r.flags & L.TILE_HELPER)) for t, r in sorted(_TILES.items()) if r.family == L.TILE_IGEMM}
+# id -> (TH, TW, BN) of the tiles each search walks: the 3x3 / stride 1 families, stride 2, transposed stride 2, the 7x7 window
+PATCH_CFGS = _geom(lambda r: r.family in (L.TILE_PATCH, L.TILE_PP, L.TILE_PP2, L.TILE_PP3, L.TILE_ONE) and not r.flags & L.TILE_ABLATION)
+S2_CFGS = _geom(lambda r: r.family == L.TILE_S2)
+T2_CFGS = _geom(lambda r: r.family in (L.TILE_T2, L.TILE_T2_ONE))
+# (the 7x7 window tiles are offered to the tile search unless V2V_S7_PATCH=0)
+S7_CFGS = _geom(lambda r: r.family == L.TILE_S7)
+ABLATION_TILES = _geom(lambda r: r.flags & L.TILE_ABLATION)     # never auto-selected
+# paired launches the engine searches: the library also pairs the ablation instances, the engine never offers them
+PAIR_TILES = tuple(t for t, r in sorted(_TILES.items()) if r.flags & L.TILE_GROUPED and not r.flags & L.TILE_ABLATION)
+# backward-data as a "full" (pad 2) 3x3 convolution: same rule
+BWD_PATCH_TILES = tuple(t for t, r in sorted(_TILES.items()) if r.flags & L.TILE_PAD2 and not r.flags & L.TILE_ABLATION)
+ONE_TILES = tuple(t for t, r in sorted(_TILES.items()) if r.family == L.TILE_ONE)
+PERSISTENT_TILES = ONE_TILES + tuple(t for t, r in sorted(_TILES.items()) if r.family == L.TILE_T2_ONE)    # ONE statistics row per workgroup, finalize in the launch at any size
 ONE_FIN = os.environ.get("V2V_ONE_FIN", "1") != "0"             # ... finalize their <= 256 statistics rows in the launch (0: separate bn_finalize launch, for A/B)
-EXP_TILES = (143,)                                              # (140 / 141: validated and faster -- regular tiles since visits r05_v3 / r05_v6)
+EXP_TILES = tuple(t for t, r in sorted(_TILES.items()) if r.flags & L.TILE_EXPERIMENT)
 if os.environ.get("V2V_EXP_TILES", "0") == "1":
     PAIR_TILES = PAIR_TILES + EXP_TILES
-
-
-def is_patch_tile(t):
-    """Tile ids of the LDS-patch 3x3 kernels (weights in K order 1): patch 32-48, ping-pong 50-57, ping-pong 2 70-79, single-phase
-    80-99, its round-5 experiment tiles 130-139 and the persistent single-chunk tile 140; stride-2 100-109, 7x7 window 120-129."""
-    return 32 <= t < 60 or 70 <= t < 110 or 120 <= t < 150
+# families the frame-wide search treats as "ping-pong" (every LDS-patch schedule after the first patch kernel)
+_PP_FAMILIES = (L.TILE_PP, L.TILE_PP2, L.TILE_PP3, L.TILE_S7, L.TILE_S2, L.TILE_T2, L.TILE_ONE, L.TILE_T2_ONE)
 
 
 def tile_korder(t):
     """Weight packing a tile id reads: 0 tap-major class matrices (implicit-GEMM tiles, 7x7 kernels), 1 channel-chunk-major (patch
-    kernels, stride-2 patch kernel), 2 the full-tap chunk-major matrix of a transposed layer (conv3x3_t2_kernel, ids 110-119)."""
-    return 2 if 110 <= t < 120 else 1 if is_patch_tile(t) else 0
+    kernels, stride-2 patch kernel), 2 the full-tap chunk-major matrix of a transposed layer (conv3x3_t2_kernel)."""
+    return _TILES[t].korder if t in _TILES else 0
+
+
+def is_patch_tile(t):
+    """Tile ids of the LDS-patch kernels that read channel-chunk-major (korder 1) weights."""
+    return tile_korder(t) == 1
+
+
 FUSE_FINALIZE_MAX_PIXELS = 32768   # larger layers leave thousands of statistics rows: parallel two-stage finalize instead
 PREFETCH_DIST = 12          # K chunks (128 B of every weight row each) the helper wave runs ahead
 
@@ -1160,7 +1148,7 @@ class Engine:
         """V2V_OUT_NORM_ACT_NHWC (include/v2v_hip.h, "fused norm"): single-phase tiles, no split-K, every workgroup of the
         launch resident at once."""
         t, S = tile3[0], max(int(tile3[1]), 1)
-        if not (self.fused_norm and self.fused_finalize and (80 <= t < 88 or 90 <= t < 94 or t in EXP_TILES) and S == 1 and cout % vec_of(self.dtype) == 0):
+        if not (self.fused_norm and self.fused_finalize and (_flag(t, L.TILE_FUSED_NORM) or t in EXP_TILES) and S == 1 and cout % vec_of(self.dtype) == 0):
             return False
         th, tw, bn = PATCH_CFGS[t]
         if self._fused_norm_wgs is None:
@@ -1476,7 +1464,7 @@ class Engine:
             d.transposed, d.pad = 0, pc.KH - 1 - pc.pad
             d.w, d.w_korder = pc.buf.data_ptr(), 0
             return pc
-        if role == "bwd" and korder == 1 and 80 <= d.tile <= 93 and self.bwd_patch_eligible(d, mod):
+        if role == "bwd" and korder == 1 and _flag(d.tile, L.TILE_PAD2) and self.bwd_patch_eligible(d, mod):
             pc = self.packed(mod, cin_stride, role="bwd", reflect=reflect, korder=4)
             d.transposed, d.pad = 0, pc.KH - 1 - pc.pad
             d.w, d.w_korder = pc.buf.data_ptr(), 1
@@ -1605,7 +1593,7 @@ class Engine:
         if mod is not None and role == "bwd" and self.bwd_c8_eligible(d, mod):
             cands.append((61, 1, 0))          # conv7x7_c8_kernel on the tap-flipped role-swapped weights (full convolution of the head's output gradient)
         if mod is not None and role == "bwd" and self.bwd_patch_eligible(d, mod):
-            for t in (80, 81, 82, 83, 84, 85, 86, 87, 90, 91, 92, 93):
+            for t in BWD_PATCH_TILES:
                 th, tw, bn = PATCH_CFGS[t]
                 tiles = d.N * -(-d.OH // th) * -(-d.OW // tw) * -(-cout // bn)
                 ncc = d.cin_stride // (64 if self.dtype == L.BF16 else 32)
@@ -1682,13 +1670,13 @@ class Engine:
         # fastest few in isolation plus the fastest unsplit ones (split-K fills an idle chip; beside concurrent lanes it
         # only adds slab traffic)
         unsplit = [cfg for _, cfg in timed if cfg[1] <= 1]
+        pp_ = lambda t: _TILES[t].family in _PP_FAMILIES
         alts = ([cfg for _, cfg in timed[:3]] + unsplit[:3]
                 + [cfg for _, cfg in timed if cfg[0] == best[0] and cfg[1] <= 2]          # the winner's tile, less split
-                + [cfg for cfg in unsplit if 50 <= cfg[0] < 60 or cfg[0] >= 70][:1])         # the best unsplit ping-pong tile
+                + [cfg for cfg in unsplit if pp_(cfg[0])][:1])                             # the best unsplit ping-pong tile
         self._last_alts = [c for i, c in enumerate(alts) if c != best and c not in alts[:i]][:7]
         # for the heaviest shapes of a frame the whole-frame search also walks every lightly split configuration that was
         # not hopeless in isolation
-        pp_ = lambda t: 50 <= t < 60 or t >= 70
         self._last_wide = ([cfg for ms, cfg in timed if pp_(cfg[0]) and cfg[1] <= 2 and cfg != best]      # every ping-pong tile
                            + [cfg for ms, cfg in timed if not pp_(cfg[0]) and cfg[1] <= 2 and ms <= 1.7 * timed[0][0]
                               and cfg != best][:10])

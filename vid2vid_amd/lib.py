@@ -45,6 +45,18 @@ class ConvDesc(C.Structure):
     ]
 
 
+class ConvTileInfo(C.Structure):
+    """struct v2v_conv_tile_info: one row of the tile table (csrc/conv_tiles.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("id", "family", "bm", "bn", "th", "tw", "korder", "flags")]
+
+
+# V2V_TILE_FAMILY_* / V2V_TILE_* (include/v2v_hip.h)
+(TILE_IGEMM, TILE_PATCH, TILE_PP, TILE_PP2, TILE_PP3, TILE_S7, TILE_S2, TILE_T2, TILE_ONE, TILE_T2_ONE, TILE_HEAD, TILE_C8,
+ TILE_ROWSUM) = range(13)
+(TILE_GROUPED, TILE_FUSED_NORM, TILE_PAD2, TILE_SINGLE_CHUNK, TILE_PERSISTENT, TILE_HELPER, TILE_BF16_ONLY, TILE_ABLATION,
+ TILE_EXPERIMENT, TILE_EXACT_BN) = (1 << i for i in range(10))
+
+
 class OneHotNorm(C.Structure):
     """struct v2v_onehot_norm"""
     _fields_ = [
@@ -77,6 +89,8 @@ PROTOTYPES = {
     "v2v_conv_stats_rows": (C.c_int, [C.POINTER(ConvDesc)]),
     "v2v_conv_debug_clocks": (C.c_int, [_P]),
     "v2v_conv_tile_config": (C.c_int, [C.POINTER(ConvDesc)]),
+    "v2v_conv_tile_count": (C.c_int, []),
+    "v2v_conv_tile_info": (C.c_int, [_I, C.POINTER(ConvTileInfo)]),
     "v2v_conv_fused_norm_max_workgroups": (C.c_int, []),
     "v2v_fastdiv_magic": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(_I)]),
     "v2v_conv_splitk_workspace": (_L, [C.POINTER(ConvDesc), C.POINTER(_I)]),
@@ -206,6 +220,16 @@ def check(rc, what=""):
     if rc != 0:
         msg = lib.v2v_last_error()
         raise RuntimeError("v2v %s failed (code %d): %s" % (what, rc, msg.decode() if msg else ""))
+
+
+def conv_tiles():
+    """The library's tile table: {tile id: ConvTileInfo}."""
+    rows = {}
+    for i in range(lib.v2v_conv_tile_count()):
+        row = ConvTileInfo()
+        check(lib.v2v_conv_tile_info(i, C.byref(row)), "conv_tile_info")
+        rows[row.id] = row
+    return rows
 
 
 def exported_symbols():
