@@ -515,6 +515,28 @@ int v2v_warp_blend(float* img_raw, const float* flow, const float* weight, const
                    const float* gx, const float* gy,
                    int32_t N, int32_t C, int32_t H, int32_t W, int32_t align_corners, void* stream);
 
+/* v2v_warp_blend for one sample (N = 1) that also rolls the window of the last generated frames: window is fp32
+ * [slots][C][H][W], oldest first; the thread that stores img_final[c][p] copies slot k + 1 -> slot k and stores the new value into
+ * the last slot (fake_B_prev = cat(fake_B_prev[1:], fake_B), models/vid2vid_model_G.py:228, without the two device copies behind
+ * the launch).  The bilinear gather reads other threads' pixels of `prev`: prev, img_raw, fg and img_final must lie outside the
+ * window (checked) -- the caller keeps its gather source in a buffer of its own (v2v_frame_prologue's `last`). */
+int v2v_warp_blend_roll(float* img_raw, const float* flow, const float* weight, const float* prev,
+                        const float* fg, const float* mask, float* img_final, float* img_warp,
+                        const float* gx, const float* gy, float* window, int32_t slots,
+                        int32_t C, int32_t H, int32_t W, int32_t align_corners, void* stream);
+
+/* Head of an inference frame whose label stems all read the 1-byte codes, in ONE launch:
+ *   codes[T][H][W]   label | edge << 7, 127 = no label plane: bit for bit v2v_label_codes (in_u8 as there);
+ *   mask[H][W]       (optional) foreground mask of frame T - 1: bit for bit what v2v_encode_labels* writes into `mask`;
+ *   packed           (with window != NULL) NHWC activation-dtype pack [H][W][c_stride] of window = planar fp32 [win_C][H][W]: bit
+ *                    for bit v2v_pack_nchw_to_nhwc (N = 1), pad channels zero; last (optional) receives an fp32 copy of the
+ *                    window's last last_C planes.
+ * The one-hot tensor is not written.  Bytes written: T H W + 4 H W + H W c_stride elemsize + 4 last_C H W. */
+int v2v_frame_prologue(const void* labels, const void* inst, int32_t in_u8, uint8_t* codes, float* mask,
+                       const int32_t* fg_labels_dev, int32_t n_fg, int32_t T, int32_t H, int32_t W, int32_t label_nc,
+                       const float* window, int32_t win_C, void* packed, int32_t c_stride, float* last, int32_t last_C,
+                       int32_t dtype, void* stream);
+
 /* Backward of v2v_warp_blend.  raw = the PRE-blend img_raw; d_rawout = gradient w.r.t. the blended
  * img_raw output (NULL if unused); d_prev (optional) must be pre-zeroed, it is accumulated atomically
  * like ATen's grid_sampler backward.  Gradient through the border clip follows ATen

@@ -11,7 +11,10 @@
 //                                                     + edge_t(p + tap) * W[co][t*per + label_nc][tap] )
 //
 // is T gathered weight rows (plus a rare edge row) per tap: 36x fewer operations, exact in fp32.  The one-hot
-// tensor is never read -- for n_scales_spatial = 1 it is not even materialised.
+// tensor is never read by this kernel.  Whether it is written is the caller's business: the inference frame plan does not
+// materialise it when every label stem runs here -- at one spatial scale the frame's head writes the 1-byte codes, the
+// foreground mask and the window pack only (v2v_frame_prologue, csrc/pointwise.hip), with more scales the first pyramid
+// level comes straight from the maps (v2v_encode_labels_pooled); any other caller of v2v_encode_labels still gets the tensor.
 //
 // Workgroup = 256 threads = 8 x 32 output pixels x one SLICE of CS = 32 or 64 output channels (gridDim.y slices),
 // thread = pixel, CS fp32 accumulators in registers.  The packed table is [49 taps][slices][blob]: a blob is the slice's

@@ -412,6 +412,89 @@ struct LayoutOp : Op {
 };
 
 // ---------------------------------------------------------------------------------------
+// head of an inference frame at one spatial scale: label codes + foreground mask + previous-frame window pack, ONE launch
+// ---------------------------------------------------------------------------------------
+// When every label stem of the frame is a gather-sum on the 1-byte codes (csrc/onehot_stem.hip), nothing reads the one-hot tensor
+// that encode_labels_kernel writes (28 MB at 512x256, tG = 3, bf16): the frame needs the codes, the foreground mask of the newest
+// frame and the NHWC pack of the previous-frame window, three small dependent launches on one lane before the first convolution
+// could start.  Here they are one grid.  Work items [0, T*H*W): one code byte each, bit for bit label_codes_kernel; the items of
+// frame T-1 also write mask[pixel], bit for bit what encode_labels_kernel writes.  Work items behind them: one 16-byte channel
+// vector of the window pack each, bit for bit pack_nchw_to_nhwc_kernel (pad channels zero); the fp32 values of the window's last
+// `last_C` planes are also copied to `last` -- the warp's gather source, kept apart from the window that warp_blend_kernel rolls
+// in place.
+struct PrologueArgs {
+    const void* labels; const void* inst; unsigned char* codes; float* mask; const int* fg; int n_fg;
+    const float* window; void* packed; float* last;
+    int T, H, W, label_nc, win_C, c_stride, last_C;
+};
+
+template <typename T, typename LT, typename IT>
+__global__ __launch_bounds__(256) void frame_prologue_kernel(const PrologueArgs a) {
+    constexpr int VEC = ElemTraits<T>::VEC;
+    const long long hw = (long long)a.H * a.W;
+    const long long ncode = hw * a.T;
+    const int vpr = a.window ? a.c_stride / VEC : 0;
+    const long long total = ncode + hw * vpr;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const LT* labels = reinterpret_cast<const LT*>(a.labels);
+    const IT* inst = reinterpret_cast<const IT*>(a.inst);
+    T* y = reinterpret_cast<T*>(a.packed);
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        if (e < ncode) {
+            const long long t = e / hw, q = e - t * hw;
+            const int lab = (int)labels[e];
+            bool edge = false;
+            if (inst) {
+                const int py = (int)(q / a.W), px = (int)(q - (long long)py * a.W);
+                const IT* ip = inst + t * hw;
+                const IT ctr = ip[q];
+                if (px > 0)       edge |= ip[q - 1] != ctr;
+                if (px < a.W - 1) edge |= ip[q + 1] != ctr;
+                if (py > 0)       edge |= ip[q - a.W] != ctr;
+                if (py < a.H - 1) edge |= ip[q + a.W] != ctr;
+            }
+            a.codes[e] = (unsigned char)(((unsigned)lab < (unsigned)a.label_nc ? lab : 127) | (edge ? 128 : 0));
+            if (a.mask && t == a.T - 1) {
+                float m = 0.f;
+                for (int i = 0; i < a.n_fg; ++i) m += (a.fg[i] == lab) ? 1.f : 0.f;
+                a.mask[q] = fminf(fmaxf(m, 0.f), 1.f);
+            }
+        } else {
+            // consecutive threads -> consecutive pixels of one channel vector (coalesced reads), as pack_nchw_to_nhwc_kernel
+            const long long v = e - ncode;
+            const long long pix = v % hw;
+            const int cv = (int)(v / hw);
+            float vals[VEC];
+#pragma unroll
+            for (int q = 0; q < VEC; ++q) {
+                const int c = cv * VEC + q;
+                vals[q] = c < a.win_C ? a.window[c * hw + pix] : 0.f;
+                if (a.last && c < a.win_C && c >= a.win_C - a.last_C) a.last[(c - (a.win_C - a.last_C)) * hw + pix] = vals[q];
+            }
+            store_vec(y, pix * a.c_stride + cv * VEC, vals);
+        }
+    }
+}
+
+struct PrologueOp : Op {
+    PrologueArgs a; int dtype; int in_u8;
+    int launch(hipStream_t s) override {
+        const int vec = dtype == V2V_BF16 ? 8 : 4;
+        const long long hw = (long long)a.H * a.W;
+        const dim3 g(grid_for(hw * a.T + (a.window ? hw * (a.c_stride / vec) : 0))), b(256);
+        if (in_u8) {
+            if (dtype == V2V_BF16) hipLaunchKernelGGL((frame_prologue_kernel<bf16_t, unsigned char, int>), g, b, 0, s, a);
+            else                   hipLaunchKernelGGL((frame_prologue_kernel<float, unsigned char, int>), g, b, 0, s, a);
+        } else {
+            if (dtype == V2V_BF16) hipLaunchKernelGGL((frame_prologue_kernel<bf16_t, float, float>), g, b, 0, s, a);
+            else                   hipLaunchKernelGGL((frame_prologue_kernel<float, float, float>), g, b, 0, s, a);
+        }
+        return check_launch();
+    }
+    const char* name() const override { return "frame_prologue"; }
+};
+
+// ---------------------------------------------------------------------------------------
 // AvgPool2d(3, stride 2, padding 1, count_include_pad=False)
 // ---------------------------------------------------------------------------------------
 struct PoolArgs { const void* x; void* y; long long planes; int N, H, W, OH, OW, c_stride; };
@@ -552,6 +635,10 @@ struct WarpArgs {
     float* img_raw; const float* flow; const float* weight; const float* prev; const float* fg; const float* mask;
     float* img_final; float* img_warp; const float* gx; const float* gy;
     int N, C, H, W, align_corners;
+    // v2v_warp_blend_roll: the fp32 window [slots][C][H][W] of the last generated frames, oldest first, rolled by the thread that
+    // stores img_final (slot k <- slot k + 1, last slot <- img_final).  `prev` must lie outside it: the bilinear gather reads other
+    // threads' pixels.
+    float* roll = nullptr; int roll_slots = 0;
 };
 
 __global__ __launch_bounds__(256) void warp_blend_kernel(const WarpArgs a) {
@@ -586,6 +673,12 @@ __global__ __launch_bounds__(256) void warp_blend_kernel(const WarpArgs a) {
                 a.img_raw[o] = raw;
             }
             a.img_final[o] = fin;
+            if (a.roll) {                               // N == 1: o = c * hw + pix
+                float* w = a.roll + o;
+                const long long slot = (long long)a.C * hw;
+                for (int k = 0; k + 1 < a.roll_slots; ++k) w[k * slot] = w[(k + 1) * slot];
+                w[(a.roll_slots - 1) * slot] = fin;
+            }
         }
     }
 }
@@ -1195,6 +1288,47 @@ extern "C" int v2v_warp_blend(float* img_raw, const float* flow, const float* we
     }
     auto op = std::make_unique<WarpOp>();
     op->a = WarpArgs{img_raw, flow, weight, prev, fg, mask, img_final, img_warp, gx, gy, N, C, H, W, align_corners};
+    return submit(std::move(op), stream);
+}
+
+extern "C" int v2v_warp_blend_roll(float* img_raw, const float* flow, const float* weight, const float* prev,
+                                   const float* fg, const float* mask, float* img_final, float* img_warp,
+                                   const float* gx, const float* gy, float* window, int32_t slots,
+                                   int32_t C, int32_t H, int32_t W, int32_t align_corners, void* stream) {
+    if (!img_raw || !img_final || (flow && (!weight || !prev || !gx || !gy)) || (fg && !mask) || !window || slots < 1 ||
+        C < 1 || H < 1 || W < 1) {
+        set_error("warp_blend_roll: bad argument"); return V2V_EINVAL;
+    }
+    const float* wend = window + (long long)slots * C * H * W;
+    const long long frame = (long long)C * H * W;
+    auto overlaps = [&](const float* p) { return p && p + frame > window && p < wend; };
+    if (overlaps(prev) || overlaps(img_final) || overlaps(img_raw) || overlaps(fg)) {
+        set_error("warp_blend_roll: the rolled window must not overlap the gather source or the frame buffers"); return V2V_EINVAL;
+    }
+    auto op = std::make_unique<WarpOp>();
+    op->a = WarpArgs{img_raw, flow, weight, prev, fg, mask, img_final, img_warp, gx, gy, 1, C, H, W, align_corners};
+    op->a.roll = window; op->a.roll_slots = slots;
+    return submit(std::move(op), stream);
+}
+
+extern "C" int v2v_frame_prologue(const void* labels, const void* inst, int32_t in_u8, uint8_t* codes, float* mask,
+                                  const int32_t* fg_labels_dev, int32_t n_fg, int32_t T, int32_t H, int32_t W, int32_t label_nc,
+                                  const float* window, int32_t win_C, void* packed, int32_t c_stride, float* last, int32_t last_C,
+                                  int32_t dtype, void* stream) {
+    const int vec = dtype == V2V_BF16 ? 8 : 4;
+    if (!labels || !codes || T < 1 || H < 1 || W < 1 || label_nc < 1 || label_nc > 126 || (in_u8 != 0 && in_u8 != 1) ||
+        (dtype != V2V_F32 && dtype != V2V_BF16) || n_fg < 0 || (mask && n_fg > 0 && !fg_labels_dev) ||
+        (in_u8 ? ((uintptr_t)inst & 3) != 0 : (((uintptr_t)labels | (uintptr_t)inst) & 3) != 0)) {
+        set_error("frame_prologue: bad argument (label_nc <= 126)"); return V2V_EINVAL;
+    }
+    if (window && (!packed || win_C < 1 || c_stride % vec != 0 || win_C > c_stride || ((uintptr_t)packed & 15) != 0 ||
+                   (last && (last_C < 1 || last_C > win_C)))) {
+        set_error("frame_prologue: bad window pack argument"); return V2V_EINVAL;
+    }
+    auto op = std::make_unique<PrologueOp>();
+    op->a = PrologueArgs{labels, inst, codes, mask, fg_labels_dev, n_fg, window, window ? packed : nullptr, window ? last : nullptr,
+                         T, H, W, label_nc, win_C, c_stride, last_C};
+    op->dtype = dtype; op->in_u8 = in_u8;
     return submit(std::move(op), stream);
 }
 

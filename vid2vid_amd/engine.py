@@ -850,6 +850,43 @@ class Engine:
         src.codes = codes
         return codes
 
+    def frame_prologue(self, src, H, W, fg_labels, want_mask, window=None, last_C=0):
+        """Head of an inference frame whose label stems all run as gather-sums, in one launch (v2v_frame_prologue): the codes of
+        label_codes, the foreground mask of encode_labels and -- with `window`, planar fp32 (1, C, H, W) -- the NHWC pack of the
+        previous-frame window plus an fp32 copy of its last `last_C` planes (the warp's gather source).  The one-hot encoding
+        is neither allocated nor written: the returned Act has its shape (a meta tensor) and its LabelSource, which is all a
+        gather-sum stem reads.  Returns (x0, mask, packed Act or None, last or None)."""
+        labels, inst, T = src.labels, src.inst, src.T
+        u8 = labels.dtype == torch.uint8
+        if u8 and inst is not None and inst.dtype != torch.int32:
+            raise TypeError("uint8 label maps go with int32 instance maps")
+        if not u8 and (labels.dtype != torch.float32 or (inst is not None and inst.dtype != torch.float32)):
+            raise TypeError("label / instance maps must be fp32-encoded integers, or uint8 + int32")
+        per = src.label_nc + (1 if inst is not None else 0)
+        codes = torch.empty((T, H, W), dtype=torch.uint8, device=self.device)
+        self._keep(codes)
+        mask = self.empty_f32(1, 1, H, W) if want_mask else None
+        fg = None
+        if want_mask:
+            fg = self._fg_labels(fg_labels)
+            self._keep(fg)
+        packed = last = None
+        win_C = cs = 0
+        if window is not None:
+            win_C = window.shape[1]
+            packed = self.empty_act(1, H, W, win_C)
+            cs = packed.Cs
+            if last_C:
+                last = self.empty_f32(1, last_C, H, W)
+        check(lib.v2v_frame_prologue(_ptr(labels), _ptr(inst), int(u8), _ptr(codes), _ptr(mask), _ptr(fg),
+                                     0 if fg is None else fg.numel(), T, H, W, src.label_nc, _ptr(window), win_C,
+                                     _ptr(None if packed is None else packed.t), cs, _ptr(last), last_C, self.dtype, _stream()),
+              "frame_prologue")
+        self.label("frame_prologue")
+        src.codes = codes
+        x0 = Act(torch.empty((1, H, W, pad_channels(T * per, self.dtype)), dtype=self.tdtype, device="meta"), T * per, onehot=src)
+        return x0, mask, packed, last
+
     def onehot_conv(self, x, conv, want_stats=True, label="", fin=None):
         """Raw fp32 NHWC output + statistics rows of the stem convolution, computed from the label maps behind `x`.
         Returns (raw, rows, (N, OH, OW)) like conv(..., OUT_RAW_F32_NHWC, want_stats=True).  fin = (norm, ss): the
@@ -2179,7 +2216,9 @@ class Engine:
         self.label("avgpool3s2_planar")
         return out
 
-    def warp_blend(self, img_raw, flow, weight, prev, fg, mask, want_warp=False):
+    def warp_blend(self, img_raw, flow, weight, prev, fg, mask, want_warp=False, roll=None):
+        """roll: the fp32 window (slots, C, H, W) of the last generated frames, oldest first -- the launch rolls it itself
+        (v2v_warp_blend_roll; inference frame plans, N == 1).  `prev` must then be a buffer outside the window."""
         N, Cc, H, W = img_raw.shape
         if self._training() and any(t is not None and t.requires_grad for t in (img_raw, flow, weight, prev, fg)):
             from . import autograd as AG
@@ -2190,6 +2229,14 @@ class Engine:
         warp = self.empty_f32(N, Cc, H, W) if (want_warp and flow is not None) else None
         for t in (gx, gy):
             self._keep(t)
+        if roll is not None:
+            if N != 1 or tuple(roll.shape[1:]) != (Cc, H, W) or roll.dtype != torch.float32 or not roll.is_contiguous():
+                raise ValueError("warp_blend: the rolled window is fp32 (slots, C, H, W) of one sample")
+            check(lib.v2v_warp_blend_roll(_ptr(img_raw), _ptr(flow), _ptr(weight), _ptr(prev), _ptr(fg), _ptr(mask),
+                                          _ptr(final), _ptr(warp), _ptr(gx), _ptr(gy), _ptr(roll), roll.shape[0], Cc, H, W,
+                                          int(self.align_corners), _stream()), "warp_blend_roll")
+            self.label("warp_blend")
+            return final, warp
         check(lib.v2v_warp_blend(_ptr(img_raw), _ptr(flow), _ptr(weight), _ptr(prev), _ptr(fg), _ptr(mask),
                                  _ptr(final), _ptr(warp), _ptr(gx), _ptr(gy), N, Cc, H, W,
                                  int(self.align_corners), _stream()), "warp_blend")

@@ -160,6 +160,8 @@ PROTOTYPES = {
     "v2v_unpack_nhwc_to_nchw": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "v2v_add_nhwc": (C.c_int, [_P, _P, _P, _L, _I, _P]),
     "v2v_warp_blend": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "v2v_warp_blend_roll": (C.c_int, [_P] * 11 + [_I] * 5 + [_P]),
+    "v2v_frame_prologue": (C.c_int, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P]),
     "v2v_resample_flow": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "v2v_correlation_out_size": (C.c_int, [_I, _I, _I, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "v2v_correlation_forward": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

@@ -208,6 +208,11 @@ class _FramePlan:
             per_ = opt.label_nc + (1 if self.inst is not None else 0)
             gather = bool(stems) and all(eng.onehot_conv_ok(c, tG * per_, H, W) for c in stems)
             early = gather and os.environ.get("V2V_LABEL_CODES", "1") != "0"     # (A/B switch)
+            # one spatial scale, every label stem a gather-sum on the codes: nothing reads the one-hot tensor, and the codes, the
+            # foreground mask and the pack of the previous-frame window are one launch (Engine.frame_prologue)
+            fused_head = early and S == 1 and opt.label_nc <= 126 and hasattr(netG_fine, "rolls_in_tail")
+            if fused_head:
+                return self._emit_fused_head(src)
             if early:
                 eng.label_codes(src, H, W)                   # one byte per pixel: what the gather-sum stems stage from
             # (writing the one-hot tensor on the foreground tower's lane instead of in front of the towers was measured: -1.5 %,
@@ -252,6 +257,30 @@ class _FramePlan:
         else:
             last = Act(x0.t[..., (tG - 1) * per:], per)
             self.out["real_A_last"] = eng.unpack(last)[0]
+        self.conv_log = list(eng.conv_log)
+
+    def _emit_fused_head(self, src):
+        """The frame at one spatial scale with all label stems on the codes: frame_prologue | towers ... | warp_blend, which
+        rolls the window of generated frames itself where the generator ends in it (no device copies behind it).  real_A_last
+        depends on the newest label map only: it is emitted behind the foreground tower on that tower's lane, beside the
+        ResnetBlock chain, not behind the blend at the frame's tail."""
+        m, eng, opt = self.model, self.eng, self.model.opt
+        tG, H, W = opt.n_frames_G, self.H, self.W
+        netG = m.netG0
+        prev = self.prev[0]
+        x0, mask0, prev_act, last = eng.frame_prologue(src, H, W, opt.fg_labels, opt.fg, window=prev.view(1, -1, H, W),
+                                                       last_C=opt.output_nc)
+
+        def real_A_last():
+            self.out["real_A_last"] = eng.onehot_planar(self.labels[tG - 1], None if self.inst is None else self.inst[tG - 1],
+                                                        H, W, opt.label_nc)
+        roll = prev if netG.rolls_in_tail(self.use_raw_only) else None
+        fake_B, flow, weight, raw, _, _, _ = netG.emit(eng, x0, prev_act, last, mask0, None, None, None, self.use_raw_only,
+                                                       tag="G0", roll=roll, side=real_A_last)
+        if roll is None:
+            self._roll(prev, fake_B)
+        self.out["flow0"], self.out["weight0"], self.out["raw0"] = flow, weight, raw
+        self.out["fake_B"] = fake_B
         self.conv_log = list(eng.conv_log)
 
     def _roll(self, prev, fake_B):

@@ -245,16 +245,19 @@ class BaseNetwork(nn.Module):
         eng = module_engine(self, image.device)
         return eng.resample_flow(image.contiguous().float(), flow.contiguous().float())
 
-    def _tail(self, eng, img_raw, flow, weight, img_prev_nchw, img_fg, mask, use_raw_only):
-        """models/networks.py:215-230 / :309-323 as one fused launch."""
+    def _tail(self, eng, img_raw, flow, weight, img_prev_nchw, img_fg, mask, use_raw_only, roll=None):
+        """models/networks.py:215-230 / :309-323 as one fused launch.  roll: the frame plan's window of generated frames, rolled
+        by that launch (Engine.warp_blend); img_prev_nchw is then a buffer of its own."""
         do_warp = not (use_raw_only or self.no_flow)
         if not do_warp and img_fg is None:
+            if roll is not None:
+                raise RuntimeError("no blend launch in this configuration: the caller rolls the window itself")
             return img_raw, img_raw
         prev3 = img_prev_nchw[:, -3:].contiguous() if do_warp else None
         if mask is not None:
             mask = mask.contiguous().float()
         res, _ = eng.warp_blend(img_raw, flow if do_warp else None, weight if do_warp else None, prev3,
-                                img_fg, mask if img_fg is not None else None)
+                                img_fg, mask if img_fg is not None else None, roll=roll)
         if isinstance(res, tuple):          # training graph: (img_final, blended img_raw), inputs untouched
             return res
         return res, img_raw                 # inference: img_raw was blended in place
@@ -337,8 +340,11 @@ class CompositeGenerator(BaseNetwork):
         return convs
 
     def emit(self, eng, x, prev, img_prev_nchw, mask, img_feat_coarse, flow_feat_coarse, img_fg_feat_coarse,
-             use_raw_only, tag="G0"):
+             use_raw_only, tag="G0", roll=None, side=None):
         """x: Act labels (NHWC), prev: Act previous frames (NHWC), img_prev_nchw: fp32 planar.
+        roll: see _tail (rolls_in_tail says whether this configuration has the launch that does it).
+        side: a callable that emits launches nothing here depends on (the frame plan's real_A_last): called behind the
+        foreground tower, on its lane -- the one furthest off the frame's critical path -- or in front of the tail without one.
         The label tower, the image tower and the foreground tower are independent until they are summed / blended, and
         so are the image and flow branches behind the sum (models/networks.py:203-232): with `eng.lanes_enabled` (frame
         plans) they are emitted on parallel plan lanes = parallel hipGraph paths."""
@@ -349,7 +355,10 @@ class CompositeGenerator(BaseNetwork):
             f = eng.run_sequential(self.indv_down, x, name=tag + ".indv_down")
             f = eng.run_sequential(self.indv_res, f, name=tag + ".indv_res")
             feat = eng.run_sequential(self.indv_up, f, name=tag + ".indv_up")
-            return feat, eng.run_sequential(self.indv_final, feat, head_nchw=True, name=tag + ".indv_final")
+            out = feat, eng.run_sequential(self.indv_final, feat, head_nchw=True, name=tag + ".indv_final")
+            if side is not None:
+                side()
+            return out
 
         def flow_heads(flow_feat):
             both = eng.head_pair(flow_feat, self.model_final_flow, self.flow_multiplier(), self.model_final_w, 1.0,
@@ -431,12 +440,18 @@ class CompositeGenerator(BaseNetwork):
             flow, weight, flow_feat = flow_branch(down)
         if not lanes and self.use_fg_model and img_fg is None:
             img_fg_feat, img_fg = fg_tower()
+        if side is not None and not self.use_fg_model:
+            side()
         if lanes or twin:
             eng.join(1)
             if self.use_fg_model:
                 eng.join(2)
-        img_final, img_raw = self._tail(eng, img_raw, flow, weight, img_prev_nchw, img_fg, mask, use_raw_only)
+        img_final, img_raw = self._tail(eng, img_raw, flow, weight, img_prev_nchw, img_fg, mask, use_raw_only, roll=roll)
         return img_final, flow, weight, img_raw, img_feat, flow_feat, img_fg_feat
+
+    def rolls_in_tail(self, use_raw_only):
+        """Does emit end in the warp / blend launch (which can roll the window of generated frames)?"""
+        return not (use_raw_only or self.no_flow) or self.use_fg_model
 
     def forward(self, input, img_prev, mask, img_feat_coarse, flow_feat_coarse, img_fg_feat_coarse, use_raw_only):
         """Same signature / return tuple as the reference (models/networks.py:203-232).  `input`,
