@@ -206,6 +206,11 @@ int     v2v_conv_pack_weights(const float* w, void* dst, int32_t cin, int32_t ci
  * workgroup (min(tiles, compute units)); with fin_counter they also write the scale / shift record themselves (last workgroup), at any
  * layer size. */
 int     v2v_conv_stats_rows(const v2v_conv_desc* d);
+/* Rows of ONE sample when every statistics row of the launch covers pixels of one sample only -- sample n then owns rows
+ * [n r, (n + 1) r) -- else 0: one output class (no transposed stride-2 class grids), no persistent tile (one row per
+ * workgroup), and for the implicit-GEMM tiles OH*OW a multiple of the tile's bm (the spatial tiles are cut per sample).
+ * Split-K launches hand over the same rows.  What v2v_in_finalize_rows needs. */
+int     v2v_conv_stats_rows_per_sample(const v2v_conv_desc* d);
 /* Bytes of `slabs` scratch (and number of `sk_counter` ints via *tickets) the launch needs; 0 when splitk <= 1. */
 int64_t v2v_conv_splitk_workspace(const v2v_conv_desc* d, int32_t* tickets);
 /* Largest m_tiles * n_tiles (* 2 for a pair) a V2V_OUT_NORM_ACT_NHWC launch may have on this device (= its CU count). */
@@ -369,6 +374,15 @@ int     v2v_in_ticket_words(int32_t C, int32_t N);
  * finalizes it. */
 int v2v_in_stats(const void* raw, int32_t raw_dtype, int32_t c_stride_raw, const float* gamma, const float* beta, float eps,
                  float* scale_shift, void* workspace, int32_t* tickets, int32_t N, int64_t HW, int32_t C, void* stream);
+/* The same [N][4][C] record from the conv epilogue's statistics rows instead of a second read of raw: rows is
+ * [N * rows_per_sample][C][2] (sum, sum^2), sample-major (v2v_conv_stats_rows_per_sample > 0), count = OH*OW.  For sample n
+ * the four rows equal BIT FOR BIT v2v_bn_finalize(rows + n rows_per_sample C 2, rows_per_sample, C, count, ...): same row
+ * phases, same fp64 combine, the same row groups above 512 rows per sample (workspace: v2v_in_finalize_rows_workspace bytes,
+ * 8-byte aligned; may be NULL up to 512).  The sample is a grid dimension; no tickets, no waiting between workgroups;
+ * no running statistics. */
+int64_t v2v_in_finalize_rows_workspace(int32_t rows_per_sample, int32_t C, int32_t N);
+int v2v_in_finalize_rows(const float* rows, int32_t rows_per_sample, int32_t N, int32_t C, int64_t count,
+                         const float* gamma, const float* beta, float eps, float* scale_shift, void* workspace, void* stream);
 /* v2v_bn_apply / v2v_bn_apply_raw / v2v_bn_apply_x3 with the scale / shift rows of sample n = pixel / HW:
  * y = act(raw * scale[n][c] + shift[n][c]) (+ add0) (+ add1), y / add0 / add1 NHWC `dtype` [N*HW][c_stride], channels >= C
  * of y written 0.  x3: NULL, or (fp32, c_stride == C, C % 4 == 0) the bf16x3 operand [hi | lo | hi] of the result. */
@@ -412,6 +426,11 @@ int v2v_onehot_planar(const float* labels, const float* inst, float* out, int32_
                       int32_t label_nc, void* stream);
 int v2v_onehot_planar_u8(const uint8_t* labels, const int32_t* inst, float* out, int32_t H, int32_t W,
                          int32_t label_nc, void* stream);
+/* N frames in one launch (sample = grid dimension): sample n reads its maps at element offset n * in_stride (one frame of a
+ * [N][T][H][W] stack; in_u8 as v2v_frame_prologue) and writes out[n][label_nc + (inst != NULL)][H][W]; sample n equals bit
+ * for bit the one-frame call on its maps. */
+int v2v_onehot_planar_batch(const void* labels, const void* inst, int32_t in_u8, float* out, int32_t N, int64_t in_stride,
+                            int32_t H, int32_t W, int32_t label_nc, void* stream);
 
 /* Instance-wise average pooling of Encoder.forward (models/networks.py:621-632) for ONE sample: out[c][p] = mean of
  * feat[c][q] over the pixels q with inst[q] == inst[p].  feat / out: planar fp32 [C][HW]; inst: fp32 [HW] holding integer ids
@@ -525,6 +544,14 @@ int v2v_warp_blend_roll(float* img_raw, const float* flow, const float* weight, 
                         const float* gx, const float* gy, float* window, int32_t slots,
                         int32_t C, int32_t H, int32_t W, int32_t align_corners, void* stream);
 
+/* v2v_warp_blend_roll for N samples: every tensor has a leading N, window is [N][slots][C][H][W] and each sample rolls its own
+ * slots; sample n equals bit for bit the one-sample call on its tensors.  No frame buffer of any sample may overlap the window of
+ * any sample (checked). */
+int v2v_warp_blend_roll_batch(float* img_raw, const float* flow, const float* weight, const float* prev,
+                              const float* fg, const float* mask, float* img_final, float* img_warp,
+                              const float* gx, const float* gy, float* window, int32_t slots,
+                              int32_t N, int32_t C, int32_t H, int32_t W, int32_t align_corners, void* stream);
+
 /* Head of an inference frame whose label stems all read the 1-byte codes, in ONE launch:
  *   codes[T][H][W]   label | edge << 7, 127 = no label plane: bit for bit v2v_label_codes (in_u8 as there);
  *   mask[H][W]       (optional) foreground mask of frame T - 1: bit for bit what v2v_encode_labels* writes into `mask`;
@@ -536,6 +563,12 @@ int v2v_frame_prologue(const void* labels, const void* inst, int32_t in_u8, uint
                        const int32_t* fg_labels_dev, int32_t n_fg, int32_t T, int32_t H, int32_t W, int32_t label_nc,
                        const float* window, int32_t win_C, void* packed, int32_t c_stride, float* last, int32_t last_C,
                        int32_t dtype, void* stream);
+/* The same for N streams in one launch (sample = grid dimension): labels / inst / codes [N][T][H][W], mask [N][H][W], window
+ * [N][win_C][H][W], packed [N][H][W][c_stride], last [N][last_C][H][W]; sample n equals bit for bit the one-sample call. */
+int v2v_frame_prologue_batch(const void* labels, const void* inst, int32_t in_u8, uint8_t* codes, float* mask,
+                             const int32_t* fg_labels_dev, int32_t n_fg, int32_t N, int32_t T, int32_t H, int32_t W,
+                             int32_t label_nc, const float* window, int32_t win_C, void* packed, int32_t c_stride,
+                             float* last, int32_t last_C, int32_t dtype, void* stream);
 
 /* Backward of v2v_warp_blend.  raw = the PRE-blend img_raw; d_rawout = gradient w.r.t. the blended
  * img_raw output (NULL if unused); d_prev (optional) must be pre-zeroed, it is accumulated atomically
@@ -746,6 +779,13 @@ int     v2v_onehot_conv7x7_norm(const void* labels, const void* inst, int32_t in
                                 float* out, float* stats, int32_t T, int32_t H, int32_t W, int32_t label_nc,
                                 int32_t cout, int32_t cout_stride, int32_t dtype, int32_t slice, const v2v_onehot_norm* fin,
                                 void* stream);
+/* v2v_onehot_conv7x7 for N streams in one launch (sample = grid dimension): labels / inst [N][T][H][W] (or the codes of
+ * v2v_frame_prologue_batch), out [N][H][W][cout_stride], stats [N * v2v_onehot_conv_stats_rows(H, W)][cout][2] sample-major
+ * (what v2v_in_finalize_rows reads); the table is read once for all samples' tiles.  Sample n equals bit for bit the
+ * one-sample call on its maps.  No in-kernel finalize (it is batch-wide). */
+int     v2v_onehot_conv7x7_batch(const void* labels, const void* inst, int32_t in_u8, const void* table, const float* bias,
+                                 float* out, float* stats, int32_t N, int32_t T, int32_t H, int32_t W, int32_t label_nc,
+                                 int32_t cout, int32_t cout_stride, int32_t dtype, int32_t slice, void* stream);
 
 /* recordable device-to-device copy (rolling fake_B_prev window, vid2vid_model_G.py:228) */
 int v2v_memcpy_d2d(void* dst, const void* src, int64_t bytes, void* stream);

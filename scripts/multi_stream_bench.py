@@ -1,0 +1,114 @@
+#!/usr/bin/env python3
+"""Multi-stream inference: ms per frame-plan replay and aggregate frames/s for B sequences per plan.
+
+bench.py's flagship configuration (label2city 512x256, one spatial scale, --fg, ngf 128, bf16, random-init weights seeded as
+there, flow head scaled to a few pixels) and its seeded synthetic inputs, stream b drawn with seed 1234 + b.  For every B the
+plan is built once (tile search included), the sequence is started, and the steady plan's graph is replayed: `rounds` rounds,
+alternating over the B values inside a round so that clock and thermal drift hits all of them alike; per B the median over the
+rounds of (ms per replay) is reported, with min and max.  aggregate frames/s = B / (ms per replay).
+
+    python scripts/multi_stream_bench.py [--streams 1,2,4,8] [--rounds 7] [--replays 40] [--json profiles/multi_stream_bench.json]
+    python scripts/multi_stream_bench.py --streams 4 --rounds 1 --trace     # a short run to put under a kernel tracer
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--streams", default="1,2,4,8")
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--replays", type=int, default=40)
+    ap.add_argument("--width", type=int, default=512)
+    ap.add_argument("--height", type=int, default=256)
+    ap.add_argument("--precision", default="bf16")
+    ap.add_argument("--ngf", type=int, default=128)
+    ap.add_argument("--json", default="")
+    ap.add_argument("--trace", action="store_true", help="no per-op table, few replays: for a run under a kernel tracer")
+    args = ap.parse_args()
+    import torch
+    from vid2vid_amd import synthetic
+    from vid2vid_amd.options import make_opt
+    from vid2vid_amd.models import create_model
+
+    H, W = args.height, args.width
+    dev = torch.device("cuda", 0)
+    Bs = [int(v) for v in args.streams.split(",")]
+    opt = make_opt(label_nc=35, use_instance=True, fg=True, use_real_img=True, random_init_ok=True, loadSize=W,
+                   precision=args.precision, gpu_ids=[0], n_scales_spatial=1, ngf=args.ngf)
+    torch.manual_seed(0)
+    model = create_model(opt)
+    with torch.no_grad():
+        model.netG0.model_final_flow[1].weight.mul_(0.1)
+    tG = opt.n_frames_G
+    seqs = [synthetic.label2city_sequence(tG + 2, H, W, seed=1234 + b, device=dev) for b in range(max(Bs))]
+
+    def inputs(B, t):
+        A = torch.stack([s[0][t:t + tG] for s in seqs[:B]]).view(B, tG, 1, H, W)
+        I = torch.stack([s[1][t:t + tG] for s in seqs[:B]]).view(B, tG, 1, H, W)
+        F0 = torch.cat([s[2][:, :tG - 1] for s in seqs[:B]]) if t == 0 else None
+        return A, F0, I
+
+    plans = {}
+    for B in Bs:                                   # build: first-frame plan is the steady plan here (use_real_img)
+        model.fake_B_prev = None
+        for t in range(2):
+            fake, _ = model.inference(*inputs(B, t))
+        assert tuple(fake.shape) == (B, 3, H, W) and bool(torch.isfinite(fake).all())
+        plans[B] = model._active_plan
+    torch.cuda.synchronize(dev)
+
+    def time_plan(fp, n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(4):
+            fp.plan.launch()
+        e0.record()
+        for _ in range(n):
+            fp.plan.launch()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    samples = {B: [] for B in Bs}
+    for r in range(args.rounds):
+        for B in (Bs if r % 2 == 0 else Bs[::-1]):
+            samples[B].append(time_plan(plans[B], args.replays))
+    rows = []
+    for B in Bs:
+        v = sorted(samples[B])
+        med = v[len(v) // 2]
+        fp = plans[B]
+        names = [n for n, _, _ in fp.plan.profile()] if not args.trace else []
+        rows.append(dict(streams=B, ms_per_replay=round(med, 4), ms_min=round(v[0], 4), ms_max=round(v[-1], 4),
+                         aggregate_frames_per_s=round(B / med * 1e3, 2), launches=fp.plan.num_ops,
+                         in_finalize_rows=names.count("in_finalize_rows"), in_stats=names.count("in_stats"),
+                         paired_convs=sum(1 for c in fp.conv_log if c.get("pair"))))
+    base = next((r for r in rows if r["streams"] == 1), None)
+    for r in rows:
+        r["vs_single_stream"] = round(r["aggregate_frames_per_s"] / base["aggregate_frames_per_s"], 4) if base else None
+    per_op = {}
+    if not args.trace:
+        for B in Bs:                               # where the time goes: per op kind, one eager timed pass of the plan
+            acc = {}
+            for name, label, ms in plans[B].plan.profile():
+                acc[name] = acc.get(name, 0.0) + ms
+            per_op[str(B)] = {k: round(v, 4) for k, v in sorted(acc.items(), key=lambda kv: -kv[1])}
+    out = dict(config="label2city %dx%d S=1 --fg ngf %d %s" % (W, H, args.ngf, args.precision), rounds=args.rounds,
+               replays_per_sample=args.replays, device=torch.cuda.get_device_name(0), table=rows, per_op_ms=per_op)
+    print("%8s %14s %22s %10s" % ("streams", "ms / replay", "aggregate frames/s", "vs B=1"))
+    for r in rows:
+        print("%8d %14.3f %22.1f %10s" % (r["streams"], r["ms_per_replay"], r["aggregate_frames_per_s"], r["vs_single_stream"]))
+    print(json.dumps(out))
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -826,6 +826,22 @@ extern "C" int v2v_conv_stats_rows(const v2v_conv_desc* d) {
     return op.ncls * op.k.m_tiles;
 }
 
+// Rows of ONE sample when every statistics row of the launch covers pixels of one sample only (sample n then owns rows
+// [n * r, (n + 1) * r): the M tiles run sample-major), else 0.  One output class only; the spatial tiles are cut per
+// sample by construction, the implicit-GEMM tiles run over N*OH*OW and qualify when OH*OW is a multiple of the tile's
+// bm; the persistent tiles leave one row per workgroup.  A split-K launch hands over the same rows (the last slice of a
+// tile runs its epilogue), exactly as for v2v_bn_finalize.
+extern "C" int v2v_conv_stats_rows_per_sample(const v2v_conv_desc* d) {
+    ConvOp op;
+    if (build_conv(d, &op, false) != 0) return V2V_EINVAL;
+    if ((op.tile->flags & V2V_TILE_PERSISTENT) || op.ncls != 1 || d->N <= 0) return 0;
+    if (op.tile->family == V2V_TILE_FAMILY_IGEMM) {
+        const long long hw = (long long)d->OH * d->OW;
+        return hw % op.tile->bm == 0 ? (int)(hw / op.tile->bm) : 0;
+    }
+    return op.k.m_tiles / d->N;
+}
+
 extern "C" int64_t v2v_conv_splitk_workspace(const v2v_conv_desc* d, int32_t* tickets) {
     ConvOp op;
     if (build_conv(d, &op, false) != 0) return V2V_EINVAL;

@@ -475,6 +475,99 @@ struct InBwdOp : Op {
     const char* name() const override { return "in_backward"; }
 };
 
+// ---------------------------------------------------------------------------------------
+// v2v_in_finalize_rows: per-sample finalize of the conv epilogue's statistics rows.  When every M tile of the conv launch
+// covers pixels of ONE sample (v2v_conv_stats_rows_per_sample), sample n owns rows [n * R, (n + 1) * R) and its statistics
+// need no second read of the raw output.  The arithmetic is v2v_bn_finalize's on that slice (csrc/norm_act.hip), bit for
+// bit: four row phases per channel in fp64, combined ((p0 + p1) + p2) + p3; more than 512 rows per sample go through the
+// same row groups first (bn_partial_reduce_kernel's cut), as a launch of its own.  A workgroup owns a (64-channel slab,
+// sample) or a (slab, row group, sample); it reads only what the previous launch wrote: no tickets, no waiting.
+// ---------------------------------------------------------------------------------------
+struct InRowsArgs {
+    const void* rows; int R; int C; int groups; double* ws;      // R: rows per sample (of the stage: conv rows, or group rows)
+    double inv_count; const float* gamma; const float* beta; float eps; float* scale_shift;
+};
+
+__global__ __launch_bounds__(256) void in_rows_partial_kernel(const InRowsArgs a) {
+    __shared__ double sh[4][64][2];
+    const int cx = threadIdx.x & 63, ph = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + cx;
+    const int g = blockIdx.y, n = blockIdx.z;
+    const float* part = reinterpret_cast<const float*>(a.rows) + (long long)n * a.R * a.C * 2;
+    const int r0 = (int)(((long long)a.R * g) / a.groups), r1 = (int)(((long long)a.R * (g + 1)) / a.groups);
+    double s1 = 0.0, s2 = 0.0;
+    if (c < a.C) {
+#pragma unroll 8
+        for (int r = r0 + ph; r < r1; r += 4) {
+            const float2 v = *reinterpret_cast<const float2*>(part + ((long long)r * a.C + c) * 2);
+            s1 += (double)v.x;
+            s2 += (double)v.y;
+        }
+    }
+    sh[ph][cx][0] = s1;
+    sh[ph][cx][1] = s2;
+    __syncthreads();
+    if (ph == 0 && c < a.C) {
+        double* dst = a.ws + (((long long)n * a.groups + g) * a.C + c) * 2;
+        dst[0] = ((sh[0][cx][0] + sh[1][cx][0]) + sh[2][cx][0]) + sh[3][cx][0];
+        dst[1] = ((sh[0][cx][1] + sh[1][cx][1]) + sh[2][cx][1]) + sh[3][cx][1];
+    }
+}
+
+template <typename R>
+__global__ __launch_bounds__(256) void in_rows_finalize_kernel(const InRowsArgs a) {
+    __shared__ double sh[4][64][2];
+    const int cx = threadIdx.x & 63, ph = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + cx;
+    const int n = blockIdx.y;
+    const R* rows_ = reinterpret_cast<const R*>(a.rows) + (long long)n * a.R * a.C * 2;
+    double s1 = 0.0, s2 = 0.0;
+    if (c < a.C) {
+#pragma unroll 8
+        for (int r = ph; r < a.R; r += 4) {
+            s1 += (double)rows_[((long long)r * a.C + c) * 2 + 0];
+            s2 += (double)rows_[((long long)r * a.C + c) * 2 + 1];
+        }
+    }
+    sh[ph][cx][0] = s1;
+    sh[ph][cx][1] = s2;
+    __syncthreads();
+    if (ph == 0 && c < a.C) {
+        s1 = ((sh[0][cx][0] + sh[1][cx][0]) + sh[2][cx][0]) + sh[3][cx][0];
+        s2 = ((sh[0][cx][1] + sh[1][cx][1]) + sh[2][cx][1]) + sh[3][cx][1];
+        const double mean = s1 * a.inv_count;
+        double var = s2 * a.inv_count - mean * mean;
+        if (var < 0.0) var = 0.0;
+        const double invstd = 1.0 / sqrt(var + (double)a.eps);
+        const double g = a.gamma ? (double)a.gamma[c] : 1.0;
+        const double b = a.beta ? (double)a.beta[c] : 0.0;
+        const double sc = g * invstd;
+        float* ss = a.scale_shift + (long long)n * 4 * a.C;
+        ss[c] = (float)sc;
+        ss[a.C + c] = (float)(b - mean * sc);
+        ss[2 * a.C + c] = (float)mean;
+        ss[3 * a.C + c] = (float)invstd;
+    }
+}
+
+struct InRowsOp : Op {
+    InRowsArgs a; int N;
+    int launch(hipStream_t s) override {
+        const unsigned slabs = (unsigned)ceil_div(a.C, 64);
+        if (a.groups > 0) {
+            hipLaunchKernelGGL(in_rows_partial_kernel, dim3(slabs, (unsigned)a.groups, (unsigned)N), dim3(256), 0, s, a);
+            int rc = check_launch(); if (rc) return rc;
+            InRowsArgs f = a;
+            f.rows = a.ws; f.R = a.groups;
+            hipLaunchKernelGGL(in_rows_finalize_kernel<double>, dim3(slabs, (unsigned)N), dim3(256), 0, s, f);
+        } else {
+            hipLaunchKernelGGL(in_rows_finalize_kernel<float>, dim3(slabs, (unsigned)N), dim3(256), 0, s, a);
+        }
+        return check_launch();
+    }
+    const char* name() const override { return "in_finalize_rows"; }
+};
+
 static bool in_geometry_ok(const char* who, int N, long long HW, int C) {
     if (N <= 0 || N > 65535 || HW <= 0 || C <= 0 || HW > (1ll << 40) / N) {
         set_error("%s: bad geometry (N=%d HW=%lld C=%d)", who, N, HW, C);
@@ -501,6 +594,31 @@ extern "C" int64_t v2v_in_workspace_bytes(int64_t HW, int32_t C, int32_t N) {
 extern "C" int v2v_in_ticket_words(int32_t C, int32_t N) {
     if (C <= 0 || N <= 0) return 0;
     return (int)(N * ceil_div(C, 64));
+}
+
+extern "C" int64_t v2v_in_finalize_rows_workspace(int32_t rows_per_sample, int32_t C, int32_t N) {
+    if (rows_per_sample <= 0 || C <= 0 || N <= 0) return 0;
+    return (int64_t)N * v2v_bn_finalize_groups(rows_per_sample) * C * 2 * 8;
+}
+
+extern "C" int v2v_in_finalize_rows(const float* rows, int32_t rows_per_sample, int32_t N, int32_t C, int64_t count,
+                                    const float* gamma, const float* beta, float eps, float* scale_shift, void* workspace,
+                                    void* stream) {
+    if (!in_geometry_ok("in_finalize_rows", N, count, C)) return V2V_EINVAL;
+    if (!rows || !scale_shift || rows_per_sample <= 0 || (long long)rows_per_sample * N > 0x7fffffffll) {
+        set_error("in_finalize_rows: bad argument"); return V2V_EINVAL;
+    }
+    const int groups = v2v_bn_finalize_groups(rows_per_sample);
+    if (groups > 0 && (!workspace || (((uintptr_t)workspace) & 7))) {
+        set_error("in_finalize_rows: %d rows per sample need the fp64 workspace (v2v_in_finalize_rows_workspace)", rows_per_sample);
+        return V2V_EINVAL;
+    }
+    auto op = std::make_unique<InRowsOp>();
+    InRowsArgs& a = op->a;
+    a.rows = rows; a.R = rows_per_sample; a.C = C; a.groups = groups; a.ws = reinterpret_cast<double*>(workspace);
+    a.inv_count = 1.0 / (double)count; a.gamma = gamma; a.beta = beta; a.eps = eps; a.scale_shift = scale_shift;
+    op->N = N;
+    return submit(std::move(op), stream);
 }
 
 extern "C" int v2v_in_stats(const void* raw, int32_t raw_dtype, int32_t c_stride_raw, const float* gamma, const float* beta, float eps,

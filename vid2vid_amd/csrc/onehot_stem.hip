@@ -80,8 +80,8 @@ inline size_t os_xoff(int T, int blob) {
 inline size_t os_xbytes(int T, int ksteps) { return (size_t)((T * OS_PHW + 15) & ~15) + (size_t)ksteps * 32 + 16; }
 inline size_t os_etab_bytes(int slices, int cs, int ksteps) { return (size_t)slices * ((cs + 31) / 32) * ksteps * 64 * 16; }
 
-// NT: frames per input (n_frames_G), 0 = run-time loop
-template <typename T, int CS, int NT>
+// NT: frames per input (n_frames_G), 0 = run-time loop; BATCH = false is the one-sample kernel as it always was
+template <typename T, int CS, int NT, bool BATCH>
 __global__ __launch_bounds__(256, CS == 64 ? 4 : 6) void onehot_conv7x7_kernel(const OneHotConvArgs a) {
     constexpr int ES = (int)sizeof(T);
     constexpr int ROWB = os_rowb(CS, ES);
@@ -107,6 +107,11 @@ __global__ __launch_bounds__(256, CS == 64 ? 4 : 6) void onehot_conv7x7_kernel(c
     const int py = tid >> 5, px = tid & 31;
     const int H = a.H, W = a.W;
     const long long hw = (long long)H * W;
+    // sample blockIdx.z (v2v_onehot_conv7x7_batch): its [T][H][W] maps, its raw output, its statistics rows
+    const long long nb = BATCH ? (long long)blockIdx.z : 0ll;
+    const char* const lab_b = reinterpret_cast<const char*>(a.labels) + nb * nT * hw * (a.in_u8 ? 1 : 4);
+    const char* const inst_b = a.inst ? reinterpret_cast<const char*>(a.inst) + nb * nT * hw * 4 : nullptr;
+    float* const out_b = a.out + nb * hw * a.cout_stride;
     const int npieces = a.blob >> 10;
     const char* const tslice = a.table + (long long)blockIdx.y * a.blob;
     const long long tap_stride = (long long)gridDim.y * a.blob;
@@ -135,13 +140,13 @@ __global__ __launch_bounds__(256, CS == 64 ? 4 : 6) void onehot_conv7x7_kernel(c
         int lab;
         bool edge = false;
         if (a.in_u8 == 2) {                                 // v2v_label_codes: label | edge << 7, 127 = no label plane
-            const int code = reinterpret_cast<const unsigned char*>(a.labels)[p];
+            const int code = reinterpret_cast<const unsigned char*>(lab_b)[p];
             lab = (code & 127) == 127 ? -1 : (code & 127);
             edge = (code & 128) != 0;
         } else if (a.in_u8) {
-            lab = reinterpret_cast<const unsigned char*>(a.labels)[p];
+            lab = reinterpret_cast<const unsigned char*>(lab_b)[p];
             if (a.inst) {
-                const int* ip = reinterpret_cast<const int*>(a.inst) + (long long)t * hw;
+                const int* ip = reinterpret_cast<const int*>(inst_b) + (long long)t * hw;
                 const int ctr = ip[q];
                 if (x > 0)     edge |= ip[q - 1] != ctr;
                 if (x < W - 1) edge |= ip[q + 1] != ctr;
@@ -149,9 +154,9 @@ __global__ __launch_bounds__(256, CS == 64 ? 4 : 6) void onehot_conv7x7_kernel(c
                 if (y < H - 1) edge |= ip[q + W] != ctr;
             }
         } else {
-            lab = (int)reinterpret_cast<const float*>(a.labels)[p];
+            lab = (int)reinterpret_cast<const float*>(lab_b)[p];
             if (a.inst) {
-                const float* ip = reinterpret_cast<const float*>(a.inst) + (long long)t * hw;
+                const float* ip = reinterpret_cast<const float*>(inst_b) + (long long)t * hw;
                 const float ctr = ip[q];
                 if (x > 0)     edge |= ip[q - 1] != ctr;
                 if (x < W - 1) edge |= ip[q + 1] != ctr;
@@ -300,7 +305,7 @@ __global__ __launch_bounds__(256, CS == 64 ? 4 : 6) void onehot_conv7x7_kernel(c
             const int oh = oh0 + (p >> 5), ow = ow0 + (p & 31);
             const int c = c0 + k * 32 + c4;
             if (oh < H && ow < W && c4 < CW && c < a.cout) {
-                float* op = a.out + ((long long)oh * W + ow) * a.cout_stride + c;
+                float* op = out_b + ((long long)oh * W + ow) * a.cout_stride + c;
                 const float* tp = tile + p * 33 + c4;
                 if (c + 4 <= a.cout && (a.cout_stride & 3) == 0) *reinterpret_cast<float4*>(op) = make_float4(tp[0], tp[1], tp[2], tp[3]);
                 else for (int e = 0; e < 4 && c + e < a.cout; ++e) op[e] = tp[e];
@@ -321,7 +326,7 @@ __global__ __launch_bounds__(256, CS == 64 ? 4 : 6) void onehot_conv7x7_kernel(c
             float t1 = 0.f, t2 = 0.f;
 #pragma unroll
             for (int part = 0; part < 8; ++part) { t1 += red[(part * 32 + tid) * 2]; t2 += red[(part * 32 + tid) * 2 + 1]; }
-            float* dst = a.stats + ((long long)blockIdx.x * a.cout + c0 + k * 32 + tid) * 2;
+            float* dst = a.stats + ((BATCH ? nb * gridDim.x + blockIdx.x : (long long)blockIdx.x) * a.cout + c0 + k * 32 + tid) * 2;
             if (a.fin_counter != nullptr) {          // read back by the finalizing workgroup: agent-scope write-through store
                 const unsigned long long bits = (unsigned long long)__float_as_uint(t1) | ((unsigned long long)__float_as_uint(t2) << 32);
                 __hip_atomic_store(reinterpret_cast<unsigned long long*>(dst), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -377,16 +382,17 @@ __global__ __launch_bounds__(256, CS == 64 ? 4 : 6) void onehot_conv7x7_kernel(c
 }
 
 struct OneHotConvOp : Op {
-    OneHotConvArgs a; int dtype, cs, slices, tiles;
-    template <typename T, int CS, int NT> int go(hipStream_t s) {
+    OneHotConvArgs a; int dtype, cs, slices, tiles; int N = 1;
+    template <typename T, int CS, int NT> int go(hipStream_t s) { return N > 1 ? go_b<T, CS, NT, true>(s) : go_b<T, CS, NT, false>(s); }
+    template <typename T, int CS, int NT, bool BATCH> int go_b(hipStream_t s) {
         const size_t lds = (size_t)a.xoff + os_xbytes(a.T, a.ksteps);
-        auto kern = onehot_conv7x7_kernel<T, CS, NT>;
+        auto kern = onehot_conv7x7_kernel<T, CS, NT, BATCH>;
         static bool attr_done = false;
         if (!attr_done) {
             hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             attr_done = true;
         }
-        hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)slices), dim3(256), (lds + 15) / 16 * 16, s, a);
+        hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)slices, (unsigned)N), dim3(256), (lds + 15) / 16 * 16, s, a);
         return check_launch();
     }
     template <typename T, int CS> int go_t(hipStream_t s) { return a.T == 3 ? go<T, CS, 3>(s) : go<T, CS, 0>(s); }
@@ -559,7 +565,11 @@ extern "C" int v2v_onehot_conv_stats_rows(int32_t H, int32_t W) {
 
 static int onehot_conv_submit(const void* labels, const void* inst, int32_t in_u8, const void* table, const float* bias,
                               float* out, float* stats, int32_t T, int32_t H, int32_t W, int32_t label_nc,
-                              int32_t cout, int32_t cout_stride, int32_t dtype, int32_t slice, const v2v_onehot_norm* fin, void* stream) {
+                              int32_t cout, int32_t cout_stride, int32_t dtype, int32_t slice, const v2v_onehot_norm* fin, void* stream,
+                              int32_t N = 1) {
+    if (N < 1 || N > 65535 || (N > 1 && fin != nullptr)) {
+        set_error("onehot_conv7x7: bad sample count %d (the in-kernel finalize is batch-wide: one sample only)", N); return V2V_EINVAL;
+    }
     if (!labels || !table || !out || T < 1 || H < 4 || W < 4 || label_nc < 1 || cout_stride < cout || !onehot_args_ok(1, cout, dtype, slice) ||
         in_u8 < 0 || in_u8 > 2 || (in_u8 == 2 && label_nc > 126)) {
         set_error("onehot_conv7x7: bad argument (cout <= 128, slice 0 / 32 / 64, image at least 4x4 for the 3-pixel mirror)"); return V2V_EINVAL;
@@ -591,7 +601,7 @@ static int onehot_conv_submit(const void* labels, const void* inst, int32_t in_u
         a.fin_inv_count = 1.0 / (double)fin->count;
         a.fin_unbias = fin->count > 1 ? (double)fin->count / (double)(fin->count - 1) : 1.0;
     }
-    op->dtype = dtype; op->cs = cs; op->slices = (int)ceil_div(cout, cs);
+    op->dtype = dtype; op->cs = cs; op->slices = (int)ceil_div(cout, cs); op->N = N;
     op->tiles = (int)(ceil_div(H, OS_TH) * ceil_div(W, OS_TW));
     return submit(std::move(op), stream);
 }
@@ -608,4 +618,10 @@ extern "C" int v2v_onehot_conv7x7_norm(const void* labels, const void* inst, int
                                        void* stream) {
     if (!fin) { set_error("onehot_conv7x7_norm: fin is NULL"); return V2V_EINVAL; }
     return onehot_conv_submit(labels, inst, in_u8, table, bias, out, stats, T, H, W, label_nc, cout, cout_stride, dtype, slice, fin, stream);
+}
+
+extern "C" int v2v_onehot_conv7x7_batch(const void* labels, const void* inst, int32_t in_u8, const void* table, const float* bias,
+                                        float* out, float* stats, int32_t N, int32_t T, int32_t H, int32_t W, int32_t label_nc,
+                                        int32_t cout, int32_t cout_stride, int32_t dtype, int32_t slice, void* stream) {
+    return onehot_conv_submit(labels, inst, in_u8, table, bias, out, stats, T, H, W, label_nc, cout, cout_stride, dtype, slice, nullptr, stream, N);
 }

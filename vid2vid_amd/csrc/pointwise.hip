@@ -426,9 +426,11 @@ struct PrologueArgs {
     const void* labels; const void* inst; unsigned char* codes; float* mask; const int* fg; int n_fg;
     const float* window; void* packed; float* last;
     int T, H, W, label_nc, win_C, c_stride, last_C;
+    int N = 1;       // v2v_frame_prologue_batch: blockIdx.y is the sample, every tensor has a leading N (dense)
 };
 
-template <typename T, typename LT, typename IT>
+// BATCH = false is the one-sample kernel as it always was (sample 0, no offsets)
+template <typename T, typename LT, typename IT, bool BATCH>
 __global__ __launch_bounds__(256) void frame_prologue_kernel(const PrologueArgs a) {
     constexpr int VEC = ElemTraits<T>::VEC;
     const long long hw = (long long)a.H * a.W;
@@ -436,9 +438,14 @@ __global__ __launch_bounds__(256) void frame_prologue_kernel(const PrologueArgs 
     const int vpr = a.window ? a.c_stride / VEC : 0;
     const long long total = ncode + hw * vpr;
     const long long stride = (long long)gridDim.x * blockDim.x;
-    const LT* labels = reinterpret_cast<const LT*>(a.labels);
-    const IT* inst = reinterpret_cast<const IT*>(a.inst);
-    T* y = reinterpret_cast<T*>(a.packed);
+    const long long nb = BATCH ? (long long)blockIdx.y : 0ll;
+    const LT* labels = reinterpret_cast<const LT*>(a.labels) + nb * ncode;
+    const IT* inst = a.inst ? reinterpret_cast<const IT*>(a.inst) + nb * ncode : nullptr;
+    unsigned char* codes = a.codes + nb * ncode;
+    float* mask = a.mask ? a.mask + nb * hw : nullptr;
+    const float* window = a.window ? a.window + nb * a.win_C * hw : nullptr;
+    float* last = a.last ? a.last + nb * a.last_C * hw : nullptr;
+    T* y = reinterpret_cast<T*>(a.packed) + nb * hw * a.c_stride;
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
         if (e < ncode) {
             const long long t = e / hw, q = e - t * hw;
@@ -453,11 +460,11 @@ __global__ __launch_bounds__(256) void frame_prologue_kernel(const PrologueArgs 
                 if (py > 0)       edge |= ip[q - a.W] != ctr;
                 if (py < a.H - 1) edge |= ip[q + a.W] != ctr;
             }
-            a.codes[e] = (unsigned char)(((unsigned)lab < (unsigned)a.label_nc ? lab : 127) | (edge ? 128 : 0));
-            if (a.mask && t == a.T - 1) {
+            codes[e] = (unsigned char)(((unsigned)lab < (unsigned)a.label_nc ? lab : 127) | (edge ? 128 : 0));
+            if (mask && t == a.T - 1) {
                 float m = 0.f;
                 for (int i = 0; i < a.n_fg; ++i) m += (a.fg[i] == lab) ? 1.f : 0.f;
-                a.mask[q] = fminf(fmaxf(m, 0.f), 1.f);
+                mask[q] = fminf(fmaxf(m, 0.f), 1.f);
             }
         } else {
             // consecutive threads -> consecutive pixels of one channel vector (coalesced reads), as pack_nchw_to_nhwc_kernel
@@ -468,8 +475,8 @@ __global__ __launch_bounds__(256) void frame_prologue_kernel(const PrologueArgs 
 #pragma unroll
             for (int q = 0; q < VEC; ++q) {
                 const int c = cv * VEC + q;
-                vals[q] = c < a.win_C ? a.window[c * hw + pix] : 0.f;
-                if (a.last && c < a.win_C && c >= a.win_C - a.last_C) a.last[(c - (a.win_C - a.last_C)) * hw + pix] = vals[q];
+                vals[q] = c < a.win_C ? window[c * hw + pix] : 0.f;
+                if (last && c < a.win_C && c >= a.win_C - a.last_C) last[(c - (a.win_C - a.last_C)) * hw + pix] = vals[q];
             }
             store_vec(y, pix * a.c_stride + cv * VEC, vals);
         }
@@ -481,13 +488,17 @@ struct PrologueOp : Op {
     int launch(hipStream_t s) override {
         const int vec = dtype == V2V_BF16 ? 8 : 4;
         const long long hw = (long long)a.H * a.W;
-        const dim3 g(grid_for(hw * a.T + (a.window ? hw * (a.c_stride / vec) : 0))), b(256);
+        const dim3 g(grid_for(hw * a.T + (a.window ? hw * (a.c_stride / vec) : 0)), (unsigned)a.N), b(256);
+        if (a.N > 1) return go<true>(g, b, s);
+        return go<false>(g, b, s);
+    }
+    template <bool BATCH> int go(dim3 g, dim3 b, hipStream_t s) {
         if (in_u8) {
-            if (dtype == V2V_BF16) hipLaunchKernelGGL((frame_prologue_kernel<bf16_t, unsigned char, int>), g, b, 0, s, a);
-            else                   hipLaunchKernelGGL((frame_prologue_kernel<float, unsigned char, int>), g, b, 0, s, a);
+            if (dtype == V2V_BF16) hipLaunchKernelGGL((frame_prologue_kernel<bf16_t, unsigned char, int, BATCH>), g, b, 0, s, a);
+            else                   hipLaunchKernelGGL((frame_prologue_kernel<float, unsigned char, int, BATCH>), g, b, 0, s, a);
         } else {
-            if (dtype == V2V_BF16) hipLaunchKernelGGL((frame_prologue_kernel<bf16_t, float, float>), g, b, 0, s, a);
-            else                   hipLaunchKernelGGL((frame_prologue_kernel<float, float, float>), g, b, 0, s, a);
+            if (dtype == V2V_BF16) hipLaunchKernelGGL((frame_prologue_kernel<bf16_t, float, float, BATCH>), g, b, 0, s, a);
+            else                   hipLaunchKernelGGL((frame_prologue_kernel<float, float, float, BATCH>), g, b, 0, s, a);
         }
         return check_launch();
     }
@@ -638,9 +649,12 @@ struct WarpArgs {
     // v2v_warp_blend_roll: the fp32 window [slots][C][H][W] of the last generated frames, oldest first, rolled by the thread that
     // stores img_final (slot k <- slot k + 1, last slot <- img_final).  `prev` must lie outside it: the bilinear gather reads other
     // threads' pixels.
+    // With N > 1 (v2v_warp_blend_roll_batch) the window is [N][slots][C][H][W]: every sample rolls its own slots.
     float* roll = nullptr; int roll_slots = 0;
 };
 
+// ROLLB: the rolled windows of N samples ([N][slots][C][H][W]); false is the kernel as it always was
+template <bool ROLLB>
 __global__ __launch_bounds__(256) void warp_blend_kernel(const WarpArgs a) {
     const long long hw = (long long)a.H * a.W;
     const long long total = (long long)a.N * hw;
@@ -673,8 +687,8 @@ __global__ __launch_bounds__(256) void warp_blend_kernel(const WarpArgs a) {
                 a.img_raw[o] = raw;
             }
             a.img_final[o] = fin;
-            if (a.roll) {                               // N == 1: o = c * hw + pix
-                float* w = a.roll + o;
+            if (a.roll) {                               // sample n's window: [slots][C][H][W]
+                float* w = a.roll + (ROLLB ? (n * a.roll_slots * a.C + c) * hw + pix : o);
                 const long long slot = (long long)a.C * hw;
                 for (int k = 0; k + 1 < a.roll_slots; ++k) w[k * slot] = w[(k + 1) * slot];
                 w[(a.roll_slots - 1) * slot] = fin;
@@ -686,7 +700,9 @@ __global__ __launch_bounds__(256) void warp_blend_kernel(const WarpArgs a) {
 struct WarpOp : Op {
     WarpArgs a;
     int launch(hipStream_t s) override {
-        hipLaunchKernelGGL(warp_blend_kernel, dim3(grid_for((long long)a.N * a.H * a.W)), dim3(256), 0, s, a);
+        const dim3 g(grid_for((long long)a.N * a.H * a.W));
+        if (a.roll && a.N > 1) hipLaunchKernelGGL(warp_blend_kernel<true>, g, dim3(256), 0, s, a);
+        else                   hipLaunchKernelGGL(warp_blend_kernel<false>, g, dim3(256), 0, s, a);
         return check_launch();
     }
     const char* name() const override { return "warp_blend"; }
@@ -1295,18 +1311,27 @@ extern "C" int v2v_warp_blend_roll(float* img_raw, const float* flow, const floa
                                    const float* fg, const float* mask, float* img_final, float* img_warp,
                                    const float* gx, const float* gy, float* window, int32_t slots,
                                    int32_t C, int32_t H, int32_t W, int32_t align_corners, void* stream) {
+    return v2v_warp_blend_roll_batch(img_raw, flow, weight, prev, fg, mask, img_final, img_warp, gx, gy, window, slots, 1, C, H, W,
+                                     align_corners, stream);
+}
+
+extern "C" int v2v_warp_blend_roll_batch(float* img_raw, const float* flow, const float* weight, const float* prev,
+                                         const float* fg, const float* mask, float* img_final, float* img_warp,
+                                         const float* gx, const float* gy, float* window, int32_t slots,
+                                         int32_t N, int32_t C, int32_t H, int32_t W, int32_t align_corners, void* stream) {
     if (!img_raw || !img_final || (flow && (!weight || !prev || !gx || !gy)) || (fg && !mask) || !window || slots < 1 ||
-        C < 1 || H < 1 || W < 1) {
+        N < 1 || C < 1 || H < 1 || W < 1) {
         set_error("warp_blend_roll: bad argument"); return V2V_EINVAL;
     }
-    const float* wend = window + (long long)slots * C * H * W;
-    const long long frame = (long long)C * H * W;
+    // the frame buffers of ALL samples against the windows of ALL samples: no sample's gather source may lie in any rolled window
+    const float* wend = window + (long long)N * slots * C * H * W;
+    const long long frame = (long long)N * C * H * W;
     auto overlaps = [&](const float* p) { return p && p + frame > window && p < wend; };
     if (overlaps(prev) || overlaps(img_final) || overlaps(img_raw) || overlaps(fg)) {
         set_error("warp_blend_roll: the rolled window must not overlap the gather source or the frame buffers"); return V2V_EINVAL;
     }
     auto op = std::make_unique<WarpOp>();
-    op->a = WarpArgs{img_raw, flow, weight, prev, fg, mask, img_final, img_warp, gx, gy, 1, C, H, W, align_corners};
+    op->a = WarpArgs{img_raw, flow, weight, prev, fg, mask, img_final, img_warp, gx, gy, N, C, H, W, align_corners};
     op->a.roll = window; op->a.roll_slots = slots;
     return submit(std::move(op), stream);
 }
@@ -1315,7 +1340,16 @@ extern "C" int v2v_frame_prologue(const void* labels, const void* inst, int32_t 
                                   const int32_t* fg_labels_dev, int32_t n_fg, int32_t T, int32_t H, int32_t W, int32_t label_nc,
                                   const float* window, int32_t win_C, void* packed, int32_t c_stride, float* last, int32_t last_C,
                                   int32_t dtype, void* stream) {
+    return v2v_frame_prologue_batch(labels, inst, in_u8, codes, mask, fg_labels_dev, n_fg, 1, T, H, W, label_nc, window, win_C, packed,
+                                    c_stride, last, last_C, dtype, stream);
+}
+
+extern "C" int v2v_frame_prologue_batch(const void* labels, const void* inst, int32_t in_u8, uint8_t* codes, float* mask,
+                                        const int32_t* fg_labels_dev, int32_t n_fg, int32_t N, int32_t T, int32_t H, int32_t W,
+                                        int32_t label_nc, const float* window, int32_t win_C, void* packed, int32_t c_stride,
+                                        float* last, int32_t last_C, int32_t dtype, void* stream) {
     const int vec = dtype == V2V_BF16 ? 8 : 4;
+    if (N < 1 || N > 65535) { set_error("frame_prologue: bad sample count %d", N); return V2V_EINVAL; }
     if (!labels || !codes || T < 1 || H < 1 || W < 1 || label_nc < 1 || label_nc > 126 || (in_u8 != 0 && in_u8 != 1) ||
         (dtype != V2V_F32 && dtype != V2V_BF16) || n_fg < 0 || (mask && n_fg > 0 && !fg_labels_dev) ||
         (in_u8 ? ((uintptr_t)inst & 3) != 0 : (((uintptr_t)labels | (uintptr_t)inst) & 3) != 0)) {
@@ -1328,6 +1362,7 @@ extern "C" int v2v_frame_prologue(const void* labels, const void* inst, int32_t 
     auto op = std::make_unique<PrologueOp>();
     op->a = PrologueArgs{labels, inst, codes, mask, fg_labels_dev, n_fg, window, window ? packed : nullptr, window ? last : nullptr,
                          T, H, W, label_nc, win_C, c_stride, last_C};
+    op->a.N = N;
     op->dtype = dtype; op->in_u8 = in_u8;
     return submit(std::move(op), stream);
 }

@@ -154,18 +154,23 @@ struct AvgPool2Op : Op {
 // `real_A[0][0, -1]` of Vid2VidModelG.inference (models/vid2vid_model_G.py:209) produced straight from the label map:
 // 4 bytes read per pixel, (label_nc + 1) * 4 written, fully coalesced along w (the NHWC -> NCHW unpack it replaces
 // moved the same bytes with 72-byte-strided reads).
-struct OneHotArgs { const void* labels; const void* inst; float* out; int H, W, label_nc; };
+// v2v_onehot_planar_batch: blockIdx.y is the sample; its maps start in_stride elements behind the previous sample's (a frame of a
+// [N][T][H][W] stack), its output (label_nc + edge) planes behind the previous sample's.
+struct OneHotArgs { const void* labels; const void* inst; float* out; int H, W, label_nc; long long in_stride = 0; int N = 1; };
 
 // LT / IT: float (the reference's float-encoded integers) or uint8 / int32 (v2v_onehot_planar_u8)
-template <typename LT, typename IT>
+// BATCH = false is the one-frame kernel as it always was (sample 0, no offsets)
+template <typename LT, typename IT, bool BATCH>
 __global__ __launch_bounds__(256) void onehot_planar_kernel(const OneHotArgs a) {
     const long long hw = (long long)a.H * a.W;
     const long long stride = (long long)gridDim.x * blockDim.x;
-    const LT* labels = reinterpret_cast<const LT*>(a.labels);
-    const IT* inst = reinterpret_cast<const IT*>(a.inst);
+    const long long nb = BATCH ? (long long)blockIdx.y : 0ll;
+    const LT* labels = reinterpret_cast<const LT*>(a.labels) + nb * a.in_stride;
+    const IT* inst = a.inst ? reinterpret_cast<const IT*>(a.inst) + nb * a.in_stride : nullptr;
+    float* out = a.out + nb * (a.label_nc + (inst ? 1 : 0)) * hw;
     for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += stride) {
         const int lab = (int)labels[p];
-        for (int c = 0; c < a.label_nc; ++c) a.out[(long long)c * hw + p] = (c == lab) ? 1.f : 0.f;
+        for (int c = 0; c < a.label_nc; ++c) out[(long long)c * hw + p] = (c == lab) ? 1.f : 0.f;
         if (inst) {
             const int y = (int)(p / a.W), x = (int)(p - (long long)y * a.W);
             const IT v = inst[p];
@@ -174,7 +179,7 @@ __global__ __launch_bounds__(256) void onehot_planar_kernel(const OneHotArgs a) 
             if (x + 1 < a.W) e |= inst[p + 1] != v;
             if (y > 0)       e |= inst[p - a.W] != v;
             if (y + 1 < a.H) e |= inst[p + a.W] != v;
-            a.out[(long long)a.label_nc * hw + p] = e ? 1.f : 0.f;
+            out[(long long)a.label_nc * hw + p] = e ? 1.f : 0.f;
         }
     }
 }
@@ -182,9 +187,14 @@ __global__ __launch_bounds__(256) void onehot_planar_kernel(const OneHotArgs a) 
 struct OneHotOp : Op {
     OneHotArgs a; int in_u8 = 0;
     int launch(hipStream_t s) override {
-        const dim3 g(grid_for((long long)a.H * a.W)), b(256);
-        if (in_u8) hipLaunchKernelGGL((onehot_planar_kernel<unsigned char, int>), g, b, 0, s, a);
-        else       hipLaunchKernelGGL((onehot_planar_kernel<float, float>), g, b, 0, s, a);
+        const dim3 g(grid_for((long long)a.H * a.W), (unsigned)a.N), b(256);
+        if (a.N > 1) {
+            if (in_u8) hipLaunchKernelGGL((onehot_planar_kernel<unsigned char, int, true>), g, b, 0, s, a);
+            else       hipLaunchKernelGGL((onehot_planar_kernel<float, float, true>), g, b, 0, s, a);
+        } else {
+            if (in_u8) hipLaunchKernelGGL((onehot_planar_kernel<unsigned char, int, false>), g, b, 0, s, a);
+            else       hipLaunchKernelGGL((onehot_planar_kernel<float, float, false>), g, b, 0, s, a);
+        }
         return check_launch();
     }
     const char* name() const override { return "onehot_planar"; }
@@ -239,5 +249,16 @@ extern "C" int v2v_onehot_planar_u8(const uint8_t* labels, const int32_t* inst, 
     if (!labels || !out || H <= 0 || W <= 0 || label_nc <= 0 || label_nc > 256) { set_error("onehot_planar_u8: bad argument"); return V2V_EINVAL; }
     auto op = std::make_unique<OneHotOp>();
     op->a = OneHotArgs{labels, inst, out, H, W, label_nc}; op->in_u8 = 1;
+    return submit(std::move(op), stream);
+}
+
+extern "C" int v2v_onehot_planar_batch(const void* labels, const void* inst, int32_t in_u8, float* out, int32_t N, int64_t in_stride,
+                                       int32_t H, int32_t W, int32_t label_nc, void* stream) {
+    if (!labels || !out || N <= 0 || N > 65535 || H <= 0 || W <= 0 || label_nc <= 0 || (in_u8 != 0 && in_u8 != 1) || (in_u8 && label_nc > 256) ||
+        in_stride < (int64_t)H * W) {
+        set_error("onehot_planar_batch: bad argument"); return V2V_EINVAL;
+    }
+    auto op = std::make_unique<OneHotOp>();
+    op->a = OneHotArgs{labels, inst, out, H, W, label_nc}; op->a.in_stride = in_stride; op->a.N = N; op->in_u8 = in_u8;
     return submit(std::move(op), stream);
 }

@@ -584,6 +584,11 @@ class Engine:
         self._sk_counters = {}
         self._lane = 0           # current plan lane (hipGraph branch); selects the scratch set
         self._sset = 0           # scratch sub-set inside a lane: member 1 of a paired launch owns its own raw / stats / tickets
+        # set by a multi-stream frame plan (B > 1 sequences per replay): every norm group of the launches emitted
+        # meanwhile takes per-sample statistics -- nn.BatchNorm2d (training mode at batch 1 = per-sample statistics with affine
+        # parameters) as well as nn.InstanceNorm2d -- from the conv epilogue's rows where each row belongs to one sample
+        self.per_stream = False
+        self.last_rows_per_sample = 0    # of the last conv() with statistics rows while per_stream: rows of one sample, or 0
         self.twin_enabled = False    # set by the frame plan: twin chains (label / image towers, image / flow branches) as paired launches
         self.pair_override = None    # (tile, splitk) forced for every paired launch (experiments: V2V_PAIR_TILE="70,1")
         if os.environ.get("V2V_PAIR_TILE"):
@@ -835,7 +840,8 @@ class Engine:
 
     def onehot_eligible(self, x, conv, pad_mode, pad_override):
         """... straight on an encoded label Act."""
-        return (x.onehot is not None and x.N == 1
+        # (N > 1: the batched stem of a multi-stream plan, staged from the codes of the batched frame prologue)
+        return (x.onehot is not None and (x.N == 1 or (self.per_stream and x.onehot.codes is not None))
                 and self.onehot_conv_ok(conv, x.C, x.H, x.W, pad_mode, conv.padding[0] if pad_override is None else pad_override))
 
     def label_codes(self, src, H, W):
@@ -857,15 +863,18 @@ class Engine:
         is neither allocated nor written: the returned Act has its shape (a meta tensor) and its LabelSource, which is all a
         gather-sum stem reads.  Returns (x0, mask, packed Act or None, last or None)."""
         labels, inst, T = src.labels, src.inst, src.T
+        N = labels.shape[0] if labels.dim() == 4 else 1      # multi-stream plans: maps (N, T, H, W), window (N, C, H, W)
         u8 = labels.dtype == torch.uint8
         if u8 and inst is not None and inst.dtype != torch.int32:
             raise TypeError("uint8 label maps go with int32 instance maps")
         if not u8 and (labels.dtype != torch.float32 or (inst is not None and inst.dtype != torch.float32)):
             raise TypeError("label / instance maps must be fp32-encoded integers, or uint8 + int32")
+        if N > 1 and window is not None and window.shape[0] != N:
+            raise ValueError("frame_prologue: %d label streams, window of %d" % (N, window.shape[0]))
         per = src.label_nc + (1 if inst is not None else 0)
-        codes = torch.empty((T, H, W), dtype=torch.uint8, device=self.device)
+        codes = torch.empty((T, H, W) if N == 1 else (N, T, H, W), dtype=torch.uint8, device=self.device)
         self._keep(codes)
-        mask = self.empty_f32(1, 1, H, W) if want_mask else None
+        mask = self.empty_f32(N, 1, H, W) if want_mask else None
         fg = None
         if want_mask:
             fg = self._fg_labels(fg_labels)
@@ -874,17 +883,23 @@ class Engine:
         win_C = cs = 0
         if window is not None:
             win_C = window.shape[1]
-            packed = self.empty_act(1, H, W, win_C)
+            packed = self.empty_act(N, H, W, win_C)
             cs = packed.Cs
             if last_C:
-                last = self.empty_f32(1, last_C, H, W)
-        check(lib.v2v_frame_prologue(_ptr(labels), _ptr(inst), int(u8), _ptr(codes), _ptr(mask), _ptr(fg),
-                                     0 if fg is None else fg.numel(), T, H, W, src.label_nc, _ptr(window), win_C,
-                                     _ptr(None if packed is None else packed.t), cs, _ptr(last), last_C, self.dtype, _stream()),
-              "frame_prologue")
+                last = self.empty_f32(N, last_C, H, W)
+        if N == 1:
+            check(lib.v2v_frame_prologue(_ptr(labels), _ptr(inst), int(u8), _ptr(codes), _ptr(mask), _ptr(fg),
+                                         0 if fg is None else fg.numel(), T, H, W, src.label_nc, _ptr(window), win_C,
+                                         _ptr(None if packed is None else packed.t), cs, _ptr(last), last_C, self.dtype, _stream()),
+                  "frame_prologue")
+        else:
+            check(lib.v2v_frame_prologue_batch(_ptr(labels), _ptr(inst), int(u8), _ptr(codes), _ptr(mask), _ptr(fg),
+                                               0 if fg is None else fg.numel(), N, T, H, W, src.label_nc, _ptr(window), win_C,
+                                               _ptr(None if packed is None else packed.t), cs, _ptr(last), last_C, self.dtype,
+                                               _stream()), "frame_prologue_batch")
         self.label("frame_prologue")
         src.codes = codes
-        x0 = Act(torch.empty((1, H, W, pad_channels(T * per, self.dtype)), dtype=self.tdtype, device="meta"), T * per, onehot=src)
+        x0 = Act(torch.empty((N, H, W, pad_channels(T * per, self.dtype)), dtype=self.tdtype, device="meta"), T * per, onehot=src)
         return x0, mask, packed, last
 
     def onehot_conv(self, x, conv, want_stats=True, label="", fin=None):
@@ -897,10 +912,10 @@ class Engine:
             pk = self._packed_onehot[(id(conv), self.onehot_slice)] = PackedOneHot(self, conv, self.onehot_slice, src.T, src.label_nc)
         elif self.plan is None:
             pk.refresh()
-        H, W, cout = x.H, x.W, conv.out_channels
+        H, W, cout, N = x.H, x.W, conv.out_channels, x.N
         cs = (cout + 3) // 4 * 4
-        raw = self.scratch("raw", H * W * cs)
-        rows = lib.v2v_onehot_conv_stats_rows(H, W) if want_stats else 0
+        raw = self.scratch("raw", N * H * W * cs)
+        rows = N * lib.v2v_onehot_conv_stats_rows(H, W) if want_stats else 0      # sample-major: rows // N per sample
         st = self.scratch("stats", rows * cout * 2) if want_stats else None
         self._keep(pk.buf)
         if pk.bias is not None:
@@ -909,7 +924,13 @@ class Engine:
             lab_ptr, in_mode = _ptr(src.codes), 2
         else:
             lab_ptr, in_mode = _ptr(src.labels), int(src.labels.dtype == torch.uint8)
-        if fin is not None and want_stats:
+        if N > 1:
+            if fin is not None or src.codes is None:
+                raise RuntimeError("the batched gather-sum stem stages from the codes and has no in-kernel (batch-wide) finalize")
+            check(lib.v2v_onehot_conv7x7_batch(lab_ptr, _ptr(src.inst), in_mode, _ptr(pk.buf), _ptr(pk.bias), _ptr(raw), _ptr(st),
+                                               N, src.T, H, W, src.label_nc, cout, cs, self.dtype, pk.slice, _stream()),
+                  "onehot_conv7x7_batch " + label)
+        elif fin is not None and want_stats:
             norm, ss = fin
             gamma, beta, eps, mom, rm, rv = self._norm_params(norm, 1)
             key = (self._lane, self._sset)
@@ -938,10 +959,10 @@ class Engine:
         if len(self.conv_log) >= 100000:
             del self.conv_log[:]
         # flops: those of the dense convolution this launch replaces (the frame's nominal 2115 GFLOP census), flagged
-        self.conv_log.append(dict(label=label, N=1, H=H, W=W, OH=H, OW=W, cin=conv.in_channels, cout=cout, tune_key=None,
+        self.conv_log.append(dict(label=label, N=N, H=H, W=W, OH=H, OW=W, cin=conv.in_channels, cout=cout, tune_key=None,
                                   KH=7, KW=7, stride=1, transposed=False, onehot=True,
-                                  flops=2.0 * H * W * cout * conv.in_channels * 49, tile=(0, 0), splitk=1, prefetch=0))
-        return raw, rows, (1, H, W)
+                                  flops=2.0 * N * H * W * cout * conv.in_channels * 49, tile=(0, 0), splitk=1, prefetch=0))
+        return raw, rows, (N, H, W)
 
     # ---------------- primitive emitters ----------------
     def conv(self, x, mod, pad_mode=L.PAD_ZERO, pad_override=None, out_mode=L.OUT_RAW_F32_NHWC,
@@ -1082,6 +1103,8 @@ class Engine:
                 d.stats = self.scratch("stats", rows * pc.cout * 2).data_ptr()
         self._splitk_workspace(d)
         self._keep(pc.buf)
+        if self.per_stream:
+            self.last_rows_per_sample = max(int(lib.v2v_conv_stats_rows_per_sample(C.byref(d))), 0) if want_stats else 0
         check(lib.v2v_conv2d(C.byref(d), _stream()), "conv2d " + label)
         self.label(label)
         ntaps = pc.KH * pc.KW
@@ -1401,7 +1424,7 @@ class Engine:
             _, _, c1b, n1b, jb = take(mb, 0)
             na, nb = "%s.%d" % (name_a, first_index + k), "%s.%d" % (name_b, first_index + k)
             # (per-sample InstanceNorm2d at batch > 1: the paired launches finalize batch-wide -> two independent chains)
-            if not self.pair_eligible(xa, c1a, xb, c1b) or self.inst_batched(n1a, xa.N) or self.inst_batched(n1b, xb.N):
+            if not self.pair_eligible(xa, c1a, xb, c1b) or self.per_sample(n1a, xa.N) or self.per_sample(n1b, xb.N):
                 xa = self.run_resblock(ba, xa, None, na)
                 xb = self.run_resblock(bb, xb, None, nb)
                 continue
@@ -1745,10 +1768,16 @@ class Engine:
         statistics of the whole launch (fin=, fused-norm pair tiles, the persistent tiles' in-launch finalize)."""
         return isinstance(norm, nn.InstanceNorm2d) and N > 1
 
+    def per_sample(self, norm, N):
+        """inst_batched, or ANY norm layer at batch > 1 while a multi-stream inference plan is emitted (per_stream): the
+        samples are independent sequences, each normalised as a batch-1 model would."""
+        return self.inst_batched(norm, N) or (self.per_stream and N > 1 and isinstance(norm, (nn.BatchNorm2d, nn.InstanceNorm2d)))
+
     def _batchwide_params(self, norm, N):
         """_norm_params for a finalize over ALL N*OH*OW pixels of a launch: an error for a per-sample norm at batch > 1."""
-        if self.inst_batched(norm, N):
-            raise RuntimeError("InstanceNorm2d at batch %d reached a batch-wide statistics finalize (per-sample statistics needed)" % N)
+        if self.per_sample(norm, N):
+            raise RuntimeError("%s at batch %d reached a batch-wide statistics finalize (per-sample statistics needed)"
+                               % (type(norm).__name__, N))
         return self._norm_params(norm, N)
 
     def _in_scratch(self, N, HW, cout):
@@ -1757,21 +1786,30 @@ class Engine:
         tk = self.scratch("in_tickets", lib.v2v_in_ticket_words(cout, N), torch.int32, zero=True)
         return ws, tk
 
-    def inorm_apply(self, raw, shape, cout, norm, act, act_param, add0=None, add1=None, label="", ss=None):
+    def inorm_apply(self, raw, shape, cout, norm, act, act_param, add0=None, add1=None, label="", ss=None, rows_per_sample=0):
         """InstanceNorm2d at batch > 1 on the conv's raw NHWC output: v2v_in_stats (per-sample [N][4][C] scale / shift /
-        mean / invstd into `ss`, kept by the caller for the backward pass on the training path) + v2v_in_apply."""
+        mean / invstd into `ss`, kept by the caller for the backward pass on the training path) + v2v_in_apply.
+        rows_per_sample > 0 (multi-stream plans): the conv launch left N * rows_per_sample statistics rows, sample-major, in
+        the "stats" scratch -- v2v_in_finalize_rows reduces them instead of a second read of raw."""
         N, OH, OW = shape
         raw_dt = L.BF16 if raw.dtype == torch.bfloat16 else L.F32      # Engine.conv(raw_act_ok=True): V2V_OUT_RAW_ACT_NHWC
         cs_raw = (cout + 7) // 8 * 8 if raw_dt == L.BF16 else (cout + 3) // 4 * 4
         if ss is None:
             ss = self.scratch("in_scale_shift", N * 4 * cout)
         gamma, beta, eps, _, _, _ = self._norm_params(norm, N)
-        ws, tk = self._in_scratch(N, OH * OW, cout)
         for t in (gamma, beta, ss):
             if t is not None:
                 self._keep(t)
-        check(lib.v2v_in_stats(_ptr(raw), raw_dt, cs_raw, _ptr(gamma), _ptr(beta), eps, _ptr(ss), _ptr(ws), _ptr(tk),
-                               N, OH * OW, cout, _stream()), "in_stats " + label)
+        if rows_per_sample > 0:
+            st = self.scratch("stats", N * rows_per_sample * cout * 2)
+            nbytes = lib.v2v_in_finalize_rows_workspace(rows_per_sample, cout, N)
+            ws = self.scratch("in_rows_ws", nbytes // 8, torch.float64) if nbytes > 0 else None
+            check(lib.v2v_in_finalize_rows(_ptr(st), rows_per_sample, N, cout, OH * OW, _ptr(gamma), _ptr(beta), eps, _ptr(ss),
+                                           _ptr(ws), _stream()), "in_finalize_rows " + label)
+        else:
+            ws, tk = self._in_scratch(N, OH * OW, cout)
+            check(lib.v2v_in_stats(_ptr(raw), raw_dt, cs_raw, _ptr(gamma), _ptr(beta), eps, _ptr(ss), _ptr(ws), _ptr(tk),
+                                   N, OH * OW, cout, _stream()), "in_stats " + label)
         self.label(label + ".norm")
         y = self.empty_act(N, OH, OW, cout)
         y3 = self._x3_out(y)
@@ -1829,14 +1867,26 @@ class Engine:
             from . import autograd as AG
             return AG.conv_group(self, x, conv, pad_mode, pad_override, norm, act, act_param, add0, add1,
                                  head_nchw, out_scale, label)
+        if norm is not None and self.onehot_eligible(x, conv, pad_mode, pad_override) and self.per_sample(norm, x.N):
+            # batched gather-sum stem: its tiles are cut per sample, every statistics row belongs to one stream
+            raw, rows, shp = self.onehot_conv(x, conv, label=label)
+            return self.inorm_apply(raw, shp, conv.out_channels, norm, act, act_param, add0=add0, add1=add1, label=label,
+                                    rows_per_sample=rows // x.N)
         if norm is not None and self.onehot_eligible(x, conv, pad_mode, pad_override):
             ss = self.scratch("scale_shift", 4 * conv.out_channels)
             fin = (norm, ss) if self.fused_finalize else None
             raw, rows, shp = self.onehot_conv(x, conv, label=label, fin=fin)
             return self.norm_apply(raw, rows, shp, conv.out_channels, norm, act, act_param, add0=add0, add1=add1, label=label,
                                    ss=ss, finalized=fin is not None)
-        if norm is not None and self.inst_batched(norm, x.N):
+        if norm is not None and self.per_sample(norm, x.N):
             # per-sample statistics: the conv runs without statistics rows and without fin= (both are batch-wide)
+            if self.per_stream and not self._x3_ok(x, conv, pad_override, with_norm=False):
+                # multi-stream plan: statistics rows, no fin=; where every row belongs to one sample (tile table:
+                # v2v_conv_stats_rows_per_sample) they are finalized per sample, else raw is read a second time (v2v_in_stats)
+                raw, _, shp = self.conv(x, conv, pad_mode, pad_override, L.OUT_RAW_F32_NHWC, want_stats=True, label=label,
+                                        raw_act_ok=True)
+                return self.inorm_apply(raw, shp, conv.out_channels, norm, act, act_param, add0=add0, add1=add1, label=label,
+                                        rows_per_sample=self.last_rows_per_sample)
             if self._x3_ok(x, conv, pad_override, with_norm=False):
                 sub = self._x3_enter()
                 n0 = len(sub.conv_log)
@@ -2027,6 +2077,17 @@ class Engine:
         self.label("fg_mask_nhwc")
         return mask
 
+    def last_planes(self, x_nchw, k):
+        """The last k planes of every sample of planar fp32 (N, C, H, W) as a dense (N, k, H, W) tensor, by recordable copies
+        (a view where it is dense already: N == 1, or k == C)."""
+        v = x_nchw[:, -k:]
+        if v.is_contiguous():
+            return v
+        out = self.empty_f32(x_nchw.shape[0], k, x_nchw.shape[2], x_nchw.shape[3])
+        for n in range(x_nchw.shape[0]):
+            self.memcpy(out[n], v[n], out[n].numel() * 4)
+        return out
+
     def memcpy(self, dst, src, nbytes):
         check(lib.v2v_memcpy_d2d(_ptr(dst), _ptr(src), nbytes, _stream()), "memcpy_d2d")
         self.label("memcpy_d2d")
@@ -2073,14 +2134,15 @@ class Engine:
         """chunk_stride: pad the channel stride to a whole 128-byte K chunk (108 -> 128 channels) so that the
         narrow fine-scale 7x7 stems (cout <= 32) can run on the LDS-patch kernel (tile 60)."""
         per = label_nc + (1 if inst is not None else 0)
-        out = self.empty_act(1, H, W, T * per)
+        N = labels.shape[0] if labels.dim() == 4 else 1      # multi-stream plans: maps (N, T, H, W), one launch per stream
+        out = self.empty_act(N, H, W, T * per)
         if chunk_stride:
             bke = 64 if self.dtype == L.BF16 else 32
             cs = (T * per + bke - 1) // bke * bke
-            wide = torch.empty((1, H, W, cs), dtype=self.tdtype, device=self.device)
+            wide = torch.empty((N, H, W, cs), dtype=self.tdtype, device=self.device)
             self._keep(wide)
             out = Act(wide, T * per)
-        mask = self.empty_f32(1, 1, H, W) if want_mask else None
+        mask = self.empty_f32(N, 1, H, W) if want_mask else None
         fg = None
         if want_mask:
             fg = self._fg_labels(fg_labels)
@@ -2093,6 +2155,13 @@ class Engine:
             if labels.dtype != torch.float32 or (inst is not None and inst.dtype != torch.float32):
                 raise TypeError("label / instance maps must be fp32-encoded integers, or uint8 + int32")
             fn = lib.v2v_encode_labels
+        if N > 1:
+            for n in range(N):
+                check(fn(_ptr(labels[n]), _ptr(None if inst is None else inst[n]), _ptr(out.t[n]), _ptr(None if mask is None else mask[n]),
+                         T, H, W, label_nc, out.Cs, _ptr(fg), 0 if fg is None else fg.numel(), self.dtype, _stream()),
+                      "encode_labels")
+                self.label("encode_labels")
+            return out, mask          # no LabelSource: the stems run as convolutions on the encoding
         check(fn(_ptr(labels), _ptr(inst), _ptr(out.t), _ptr(mask), T, H, W, label_nc,
                  out.Cs, _ptr(fg), 0 if fg is None else fg.numel(), self.dtype, _stream()),
               "encode_labels")
@@ -2200,6 +2269,15 @@ class Engine:
     def onehot_planar(self, labels, inst, H, W, label_nc):
         """Planar fp32 one-hot (+ edge plane) of one label frame: `real_A[0][0, -1]` (vid2vid_model_G.py:209)."""
         per = label_nc + (1 if inst is not None else 0)
+        if labels.dim() == 3:         # multi-stream plans: one frame of every stream, a strided view (N, H, W) of (N, T, H, W) maps
+            N = labels.shape[0]
+            if labels.stride(1) != W or labels.stride(2) != 1 or (inst is not None and inst.stride() != labels.stride()):
+                raise ValueError("onehot_planar: dense frames, the same sample stride for labels and instance maps")
+            out = self.empty_f32(N, per, H, W)
+            check(lib.v2v_onehot_planar_batch(_ptr(labels), _ptr(inst), int(labels.dtype == torch.uint8), _ptr(out), N,
+                                              labels.stride(0), H, W, label_nc, _stream()), "onehot_planar_batch")
+            self.label("onehot_planar")
+            return out
         out = self.empty_f32(per, H, W)
         fn = lib.v2v_onehot_planar_u8 if labels.dtype == torch.uint8 else lib.v2v_onehot_planar
         check(fn(_ptr(labels), _ptr(inst), _ptr(out), H, W, label_nc, _stream()), "onehot_planar")
@@ -2218,7 +2296,8 @@ class Engine:
 
     def warp_blend(self, img_raw, flow, weight, prev, fg, mask, want_warp=False, roll=None):
         """roll: the fp32 window (slots, C, H, W) of the last generated frames, oldest first -- the launch rolls it itself
-        (v2v_warp_blend_roll; inference frame plans, N == 1).  `prev` must then be a buffer outside the window."""
+        (v2v_warp_blend_roll; inference frame plans); (N, slots, C, H, W) for the N streams of a multi-stream plan
+        (v2v_warp_blend_roll_batch).  `prev` must then be a buffer outside the window."""
         N, Cc, H, W = img_raw.shape
         if self._training() and any(t is not None and t.requires_grad for t in (img_raw, flow, weight, prev, fg)):
             from . import autograd as AG
@@ -2229,6 +2308,14 @@ class Engine:
         warp = self.empty_f32(N, Cc, H, W) if (want_warp and flow is not None) else None
         for t in (gx, gy):
             self._keep(t)
+        if roll is not None and roll.dim() == 5:
+            if tuple(roll.shape[2:]) != (Cc, H, W) or roll.shape[0] != N or roll.dtype != torch.float32 or not roll.is_contiguous():
+                raise ValueError("warp_blend: the rolled windows are fp32 (N, slots, C, H, W)")
+            check(lib.v2v_warp_blend_roll_batch(_ptr(img_raw), _ptr(flow), _ptr(weight), _ptr(prev), _ptr(fg), _ptr(mask),
+                                                _ptr(final), _ptr(warp), _ptr(gx), _ptr(gy), _ptr(roll), roll.shape[1], N, Cc, H, W,
+                                                int(self.align_corners), _stream()), "warp_blend_roll_batch")
+            self.label("warp_blend")
+            return final, warp
         if roll is not None:
             if N != 1 or tuple(roll.shape[1:]) != (Cc, H, W) or roll.dtype != torch.float32 or not roll.is_contiguous():
                 raise ValueError("warp_blend: the rolled window is fp32 (slots, C, H, W) of one sample")

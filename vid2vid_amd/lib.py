@@ -87,6 +87,7 @@ PROTOTYPES = {
     "v2v_conv_packed_elems": (_L, [_I, _I, _I, _I, _I, _I, _I, _I, _I]),
     "v2v_conv_pack_weights": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "v2v_conv_stats_rows": (C.c_int, [C.POINTER(ConvDesc)]),
+    "v2v_conv_stats_rows_per_sample": (C.c_int, [C.POINTER(ConvDesc)]),
     "v2v_conv_debug_clocks": (C.c_int, [_P]),
     "v2v_conv_tile_config": (C.c_int, [C.POINTER(ConvDesc)]),
     "v2v_conv_tile_count": (C.c_int, []),
@@ -131,6 +132,8 @@ PROTOTYPES = {
     "v2v_in_workspace_bytes": (_L, [_L, _I, _I]),
     "v2v_in_ticket_words": (C.c_int, [_I, _I]),
     "v2v_in_stats": (C.c_int, [_P, _I, _I, _P, _P, _F, _P, _P, _P, _I, _L, _I, _P]),
+    "v2v_in_finalize_rows_workspace": (_L, [_I, _I, _I]),
+    "v2v_in_finalize_rows": (C.c_int, [_P, _I, _I, _I, _L, _P, _P, _F, _P, _P, _P]),
     "v2v_in_apply": (C.c_int, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _F, _I, _P]),
     "v2v_in_backward": (C.c_int, [_P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I, _L, _I, _I, _I, _F, _I, _P]),
     "v2v_avgpool3s2_planar": (C.c_int, [_P, _P, _L, _I, _I, _P]),
@@ -141,6 +144,7 @@ PROTOTYPES = {
     "v2v_avgpool2_planar_backward": (C.c_int, [_P, _P, _L, _I, _I, _P]),
     "v2v_onehot_planar": (C.c_int, [_P, _P, _P, _I, _I, _I, _P]),
     "v2v_onehot_planar_u8": (C.c_int, [_P, _P, _P, _I, _I, _I, _P]),
+    "v2v_onehot_planar_batch": (C.c_int, [_P, _P, _I, _P, _I, _L, _I, _I, _I, _P]),
     "v2v_instance_mean_workspace": (_L, [_I, _L]),
     "v2v_instance_mean_planar": (C.c_int, [_P, _P, _P, _P, _I, _L, _P]),
     "v2v_tensor2im": (C.c_int, [_P, _P, _I, _I, _I, _I, _P]),
@@ -151,6 +155,7 @@ PROTOTYPES = {
     "v2v_onehot_conv_stats_rows": (C.c_int, [_I, _I]),
     "v2v_label_codes": (C.c_int, [_P, _P, _I, _P, _I, _I, _I, _I, _P]),
     "v2v_onehot_conv7x7": (C.c_int, [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "v2v_onehot_conv7x7_batch": (C.c_int, [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "v2v_onehot_conv7x7_norm": (C.c_int, [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(OneHotNorm), _P]),
     "v2v_encode_labels": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
     "v2v_encode_labels_u8": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
@@ -161,7 +166,9 @@ PROTOTYPES = {
     "v2v_add_nhwc": (C.c_int, [_P, _P, _P, _L, _I, _P]),
     "v2v_warp_blend": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "v2v_warp_blend_roll": (C.c_int, [_P] * 11 + [_I] * 5 + [_P]),
+    "v2v_warp_blend_roll_batch": (C.c_int, [_P] * 11 + [_I] * 6 + [_P]),
     "v2v_frame_prologue": (C.c_int, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P]),
+    "v2v_frame_prologue_batch": (C.c_int, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P]),
     "v2v_resample_flow": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "v2v_correlation_out_size": (C.c_int, [_I, _I, _I, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "v2v_correlation_forward": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

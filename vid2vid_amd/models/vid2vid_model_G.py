@@ -52,12 +52,16 @@ def nearest_face_features(feat_map, inst, features, feat_num):
 
 
 class _FramePlan:
-    """Buffers + launch sequence generating one frame at every spatial scale."""
+    """Buffers + launch sequence generating one frame at every spatial scale, for B independent sequences (streams) per
+    replay.  B == 1: the buffers have no stream dimension, exactly the single-sequence plan.  B > 1: every static
+    buffer and output gets a leading B, and every norm group is lowered with per-sample statistics (Engine.per_stream), so
+    stream b computes what a batch-1 plan computes on sequence b alone."""
 
-    def __init__(self, model, H, W, in_ch, has_inst, use_raw_only, use_graph=True, u8=False):
+    def __init__(self, model, H, W, in_ch, has_inst, use_raw_only, use_graph=True, u8=False, B=1):
         opt, eng = model.opt, model.engine
         self.model, self.eng = model, eng
-        self.H, self.W, self.use_raw_only = H, W, use_raw_only
+        self.H, self.W, self.use_raw_only, self.B = H, W, use_raw_only, B
+        lead = (B,) if B > 1 else ()
         tG, S = opt.n_frames_G, model.n_scales
         self.label_mode = opt.label_nc != 0
         dev = eng.device
@@ -65,14 +69,14 @@ class _FramePlan:
         if self.label_mode:
             # fp32-encoded integers (the reference loader's format), or uint8 labels + int32 instance ids (SURVEY 8f-2:
             # a quarter of the host-to-device bytes for the label maps; same one-hot / edge tensors bit for bit)
-            self.labels = torch.zeros(tG, H, W, dtype=torch.uint8 if u8 else torch.float32, device=dev)
-            self.inst = torch.zeros(tG, H, W, dtype=torch.int32 if u8 else torch.float32, device=dev) if has_inst else None
+            self.labels = torch.zeros(*lead, tG, H, W, dtype=torch.uint8 if u8 else torch.float32, device=dev)
+            self.inst = torch.zeros(*lead, tG, H, W, dtype=torch.int32 if u8 else torch.float32, device=dev) if has_inst else None
             self.raw_in = None
         else:
             self.labels = self.inst = None
-            self.raw_in = torch.zeros(1, tG * in_ch, H, W, dtype=torch.float32, device=dev)
-        # fake_B_prev[si]: (tG-1, 3, h, w) per scale, si = 0 finest  (reference :228, :248-250)
-        self.prev = [torch.zeros(tG - 1, opt.output_nc, H >> si, W >> si, dtype=torch.float32, device=dev)
+            self.raw_in = torch.zeros(B, tG * in_ch, H, W, dtype=torch.float32, device=dev)
+        # fake_B_prev[si]: (tG-1, 3, h, w) per scale, si = 0 finest  (reference :228, :248-250); (B, tG-1, 3, h, w) at B > 1
+        self.prev = [torch.zeros(*lead, tG - 1, opt.output_nc, H >> si, W >> si, dtype=torch.float32, device=dev)
                      for si in range(S)]
         self.out = {}
         # independent towers / branches on parallel plan lanes (parallel hipGraph paths); opt.lanes or V2V_LANES
@@ -81,11 +85,13 @@ class _FramePlan:
         self.twin = bool(int(getattr(opt, "twin", os.environ.get("V2V_TWIN", "1"))))
         eng.lanes_enabled = self.lanes
         eng.twin_enabled = self.twin
+        eng.per_stream = B > 1          # per-sample statistics for every norm group (BatchNorm2d too) while this plan is emitted
         try:
             self._build(model, opt, eng, use_graph)
         finally:
             eng.lanes_enabled = False
             eng.twin_enabled = False
+            eng.per_stream = False
 
     def _build(self, model, opt, eng, use_graph):
         dev = eng.device
@@ -197,7 +203,7 @@ class _FramePlan:
     def _emit(self):
         m, eng, opt = self.model, self.eng, self.model.opt
         tG, S = opt.n_frames_G, m.n_scales
-        H, W = self.H, self.W
+        H, W, B = self.H, self.W, self.B
         eng.conv_log = []
         # encode_input (:86-112) + compute_mask (:322-330), fused, straight to NHWC
         if self.label_mode:
@@ -213,6 +219,10 @@ class _FramePlan:
             fused_head = early and S == 1 and opt.label_nc <= 126 and hasattr(netG_fine, "rolls_in_tail")
             if fused_head:
                 return self._emit_fused_head(src)
+            if B > 1:
+                # streams off the fused head (S > 1, stems that are no gather-sums): one encode launch per stream into one
+                # batched encoding, the stems as convolutions on it -- correct through the batch-capable kernels, not fast
+                early = gather = False
             if early:
                 eng.label_codes(src, H, W)                   # one byte per pixel: what the gather-sum stems stage from
             # (writing the one-hot tensor on the foreground tower's lane instead of in front of the towers was measured: -1.5 %,
@@ -242,7 +252,7 @@ class _FramePlan:
             mask = masks[si]
             if opt.fg and mask is None:
                 mask = self._mask_from_pooled(x, per, tG)
-            prev_nchw = self.prev[si].view(1, -1, H >> si, W >> si)
+            prev_nchw = self.prev[si].view(B, -1, H >> si, W >> si)
             fake_B, flow, weight, raw, feat, flow_feat, fg_feat = netG.emit(
                 eng, x, eng.pack(prev_nchw), prev_nchw, mask, feat, flow_feat, fg_feat, self.use_raw_only,
                 tag="G%d" % s)
@@ -252,12 +262,19 @@ class _FramePlan:
         self.out["fake_B"] = fake_B
         # real_A[0][0, -1]: encoded last label frame, returned for visualisation (:209)
         if self.label_mode:      # straight from the label map: coalesced planar writes, no NHWC -> NCHW transpose
-            self.out["real_A_last"] = eng.onehot_planar(self.labels[tG - 1], None if self.inst is None else self.inst[tG - 1],
-                                                        H, W, opt.label_nc)
+            self.out["real_A_last"] = self._real_A_last()
         else:
             last = Act(x0.t[..., (tG - 1) * per:], per)
-            self.out["real_A_last"] = eng.unpack(last)[0]
+            last = eng.unpack(last)
+            self.out["real_A_last"] = last[0] if B == 1 else last
         self.conv_log = list(eng.conv_log)
+
+    def _real_A_last(self):
+        """Planar one-hot (+ edge plane) of the newest label frame: (C, H, W), or (B, C, H, W) in one launch at B > 1."""
+        tG, opt = self.model.opt.n_frames_G, self.model.opt
+        lab = self.labels[tG - 1] if self.B == 1 else self.labels[:, tG - 1]
+        inst = None if self.inst is None else (self.inst[tG - 1] if self.B == 1 else self.inst[:, tG - 1])
+        return self.eng.onehot_planar(lab, inst, self.H, self.W, opt.label_nc)
 
     def _emit_fused_head(self, src):
         """The frame at one spatial scale with all label stems on the codes: frame_prologue | towers ... | warp_blend, which
@@ -268,12 +285,11 @@ class _FramePlan:
         tG, H, W = opt.n_frames_G, self.H, self.W
         netG = m.netG0
         prev = self.prev[0]
-        x0, mask0, prev_act, last = eng.frame_prologue(src, H, W, opt.fg_labels, opt.fg, window=prev.view(1, -1, H, W),
+        x0, mask0, prev_act, last = eng.frame_prologue(src, H, W, opt.fg_labels, opt.fg, window=prev.view(self.B, -1, H, W),
                                                        last_C=opt.output_nc)
 
         def real_A_last():
-            self.out["real_A_last"] = eng.onehot_planar(self.labels[tG - 1], None if self.inst is None else self.inst[tG - 1],
-                                                        H, W, opt.label_nc)
+            self.out["real_A_last"] = self._real_A_last()
         roll = prev if netG.rolls_in_tail(self.use_raw_only) else None
         fake_B, flow, weight, raw, _, _, _ = netG.emit(eng, x0, prev_act, last, mask0, None, None, None, self.use_raw_only,
                                                        tag="G0", roll=roll, side=real_A_last)
@@ -284,6 +300,13 @@ class _FramePlan:
         self.conv_log = list(eng.conv_log)
 
     def _roll(self, prev, fake_B):
+        if self.B > 1:                   # (B, tG-1, 3, h, w) <- (B, 3, h, w): every stream rolls its own window
+            for b in range(self.B):
+                self._roll_one(prev[b], fake_B[b])
+        else:
+            self._roll_one(prev, fake_B)
+
+    def _roll_one(self, prev, fake_B):
         n = prev.shape[0]
         frame_bytes = prev[0].numel() * 4
         for k in range(n - 1):
@@ -360,40 +383,50 @@ class Vid2VidModelG(BaseModel):
         self.bind_precision()
 
     # ------------------------------------------------------------------ inference
-    def _frame_plan(self, H, W, in_ch, has_inst, use_raw_only, u8=False):
-        key = (H, W, in_ch, has_inst, use_raw_only, self.precision, u8)
+    def _frame_plan(self, H, W, in_ch, has_inst, use_raw_only, u8=False, B=1):
+        key = (H, W, in_ch, has_inst, use_raw_only, self.precision, u8, B)
         fp = self._plans.get(key)
         if fp is None:
             self.engine.refresh_weights()
             fp = _FramePlan(self, H, W, in_ch, has_inst, use_raw_only,
-                            use_graph=getattr(self.opt, "use_graph", True), u8=u8)
+                            use_graph=getattr(self.opt, "use_graph", True), u8=u8, B=B)
             self._plans[key] = fp
         return fp
 
     def inference(self, input_A, input_B, inst_A):
-        """(fake_B (1,3,H,W), real_A_last (C,H,W)) for the newest of the tG label frames in input_A."""
+        """(fake_B (B,3,H,W), real_A_last) for the newest of the tG label frames of each of the B sequences in input_A
+        (B,t,c,H,W); inst_A / input_B carry the same leading B.  B == 1: real_A_last is (C,H,W) and model.fake_B_prev a list
+        per scale of (tG-1,3,h,w), as in the reference.  B > 1 (multi-stream): real_A_last is (B,C,H,W),
+        fake_B_prev a list per scale of (B,tG-1,3,h,w), and stream b gets what a batch-1 model gets on sequence b alone.
+        Changing B inside a sequence (fake_B_prev not None) is a ValueError; fake_B_prev = None restarts all streams."""
         opt = self.opt
         tG = opt.n_frames_G
         with torch.no_grad():
-            _, t_in, in_ch, H, W = input_A.shape
+            B, t_in, in_ch, H, W = input_A.shape
             if t_in < tG:
                 raise ValueError("inference needs n_frames_G=%d label frames, got %d" % (tG, t_in))
+            for name, t in (("inst_A", inst_A if opt.use_instance else None), ("input_B", input_B)):
+                if t is not None and t.shape[0] != B:
+                    raise ValueError("inference: input_A holds %d sequence(s), %s %d" % (B, name, t.shape[0]))
             self._check_device_status()
             self.is_first_frame = not hasattr(self, "fake_B_prev") or self.fake_B_prev is None
+            if not self.is_first_frame and self._active_plan is not None and self._active_plan.B != B:
+                raise ValueError("inference: %d sequence(s) given while %d are running; assign fake_B_prev = None to restart"
+                                 % (B, self._active_plan.B))
             use_raw_only = bool(opt.no_first_img and self.is_first_frame)
             has_inst = bool(opt.use_instance and inst_A is not None and opt.label_nc != 0)
             u8 = bool(opt.label_nc != 0 and input_A.dtype == torch.uint8)
-            fp = self._frame_plan(H, W, in_ch, has_inst, use_raw_only, u8)
+            fp = self._frame_plan(H, W, in_ch, has_inst, use_raw_only, u8, B)
             dev = self.device
             # ---- stage inputs (H2D or D2D) into the plan's static buffers; pinned host tensors copy asynchronously ----
             if fp.label_mode:
-                fp.labels.copy_(input_A[0, :tG, 0].to(dev, fp.labels.dtype, non_blocking=True))
+                fp.labels.copy_((input_A[0, :tG, 0] if B == 1 else input_A[:, :tG, 0]).to(dev, fp.labels.dtype, non_blocking=True))
                 if has_inst:
-                    fp.inst.copy_(inst_A[0, :tG, 0].to(dev, fp.inst.dtype, non_blocking=True))
+                    fp.inst.copy_((inst_A[0, :tG, 0] if B == 1 else inst_A[:, :tG, 0]).to(dev, fp.inst.dtype, non_blocking=True))
             else:
-                fp.raw_in.copy_(input_A[0, :tG].reshape(1, tG * in_ch, H, W).to(dev, torch.float32, non_blocking=True))
+                fp.raw_in.copy_(input_A[:, :tG].reshape(B, tG * in_ch, H, W).to(dev, torch.float32, non_blocking=True))
             if self.is_first_frame:
-                first = self.generate_first_frame(input_A, input_B, inst_A)     # list per scale (tG-1,3,h,w)
+                first = self.generate_first_frame(input_A, input_B, inst_A)     # list per scale (tG-1,3,h,w) / (B,tG-1,3,h,w)
                 for si in range(self.n_scales):
                     fp.prev[si].copy_(first[si])
             elif self._active_plan is not fp:
@@ -427,10 +460,10 @@ class Vid2VidModelG(BaseModel):
         """Pyramid of the tG-1 frames that precede the first generated one (reference :231-251)."""
         opt = self.opt
         tG = opt.n_frames_G
-        _, _, _, H, W = input_A.shape
+        B, _, _, H, W = input_A.shape
         dev = self.device
         if opt.no_first_img:
-            first = torch.zeros(1, tG - 1, opt.output_nc, H, W, dtype=torch.float32, device=dev)
+            first = torch.zeros(B, tG - 1, opt.output_nc, H, W, dtype=torch.float32, device=dev)
         elif opt.isTrain or opt.use_real_img:
             if input_B is None:
                 raise ValueError("use_real_img needs the first real frames (input_B)")
@@ -446,17 +479,20 @@ class Vid2VidModelG(BaseModel):
                 frames.append(self.netG_i.forward(input_A[:, i].to(dev, torch.float32), feat_map).unsqueeze(1))
             first = torch.cat(frames, dim=1)
         elif opt.use_single_G:
-            frames = []
-            lab = input_A[0, :, 0].to(dev, torch.float32).contiguous()
             eng = self.engine
-            for i in range(tG - 1):       # one-hot labels only, no edge channel (reference :239-244)
-                onehot, _ = eng.encode_labels(lab[i:i + 1], None, 1, H, W, opt.label_nc, (), False)
-                frames.append(self.netG_i.emit(eng, onehot).unsqueeze(1))
-            first = torch.cat(frames, dim=1)
+            seqs = []
+            for b in range(B):                # the single-image generator runs once per sequence
+                frames = []
+                lab = input_A[b, :, 0].to(dev, torch.float32).contiguous()
+                for i in range(tG - 1):       # one-hot labels only, no edge channel (reference :239-244)
+                    onehot, _ = eng.encode_labels(lab[i:i + 1], None, 1, H, W, opt.label_nc, (), False)
+                    frames.append(self.netG_i.emit(eng, onehot).unsqueeze(1))
+                seqs.append(torch.cat(frames, dim=1))
+            first = seqs[0] if B == 1 else torch.cat(seqs, dim=0)
         else:
             raise ValueError("Please specify the method for generating the first frame")
         pyr = self.build_pyr(first.contiguous())
-        return [p[0] for p in pyr]
+        return [p[0] for p in pyr] if B == 1 else list(pyr)
 
     def load_single_G(self):
         """First-frame single-image generator (reference :261-288).  Only the Cityscapes nets are on

@@ -253,7 +253,10 @@ class BaseNetwork(nn.Module):
             if roll is not None:
                 raise RuntimeError("no blend launch in this configuration: the caller rolls the window itself")
             return img_raw, img_raw
-        prev3 = img_prev_nchw[:, -3:].contiguous() if do_warp else None
+        if do_warp and not eng._training():
+            prev3 = eng.last_planes(img_prev_nchw, 3)       # (a recorded copy at batch > 1: frame plans replay it)
+        else:
+            prev3 = img_prev_nchw[:, -3:].contiguous() if do_warp else None
         if mask is not None:
             mask = mask.contiguous().float()
         res, _ = eng.warp_blend(img_raw, flow if do_warp else None, weight if do_warp else None, prev3,
