@@ -27,6 +27,12 @@ import torch.nn as nn
 
 from . import lib as L
 from .lib import lib, check, ConvDesc
+# Which tile a launch may try -- the tile-table views, the eligibility predicates, the candidate lists -- is tile_search.py's; the
+# names that tests, scripts and bench.py read from this module stay importable from it.
+from . import tile_search as TS
+from .tile_search import (TILE_CFGS, PATCH_CFGS, S2_CFGS, T2_CFGS, S7_CFGS, ABLATION_TILES, PAIR_TILES, BWD_PATCH_TILES,      # noqa: F401
+                          ONE_TILES, PERSISTENT_TILES, ONE_FIN, EXP_TILES, HEAD_TILE, C8_TILE, ROWSUM_TILE, tile_korder,
+                          is_patch_tile, _flag, _cfg3)
 
 _TORCH_DTYPE = {L.F32: torch.float32, L.BF16: torch.bfloat16}
 
@@ -458,63 +464,8 @@ class Plan:
             pass
 
 
-# What a tile id is -- kernel family, geometry, weight packing, capabilities -- is written down once, in the library's tile table
-# (csrc/conv_tiles.h, read through v2v_conv_tile_info); the names below are views of it.
-_TILES = L.conv_tiles()
-
-
-def _geom(pick):
-    return {t: (r.th, r.tw, r.bn) for t, r in sorted(_TILES.items()) if pick(r)}
-
-
-def _flag(t, bit):
-    """Flag `bit` of tile id t; False for 0 (auto) and ids the library does not know (it refuses them)."""
-    return t in _TILES and bool(_TILES[t].flags & bit)
-
-
-# implicit-GEMM tiles: id -> (BM, BN, has a prefetch-helper instance)
-TILE_CFGS = {t: (r.bm, r.bn, bool(r.flags & L.TILE_HELPER)) for t, r in sorted(_TILES.items()) if r.family == L.TILE_IGEMM}
-# id -> (TH, TW, BN) of the tiles each search walks: the 3x3 / stride 1 families, stride 2, transposed stride 2, the 7x7 window
-PATCH_CFGS = _geom(lambda r: r.family in (L.TILE_PATCH, L.TILE_PP, L.TILE_PP2, L.TILE_PP3, L.TILE_ONE) and not r.flags & L.TILE_ABLATION)
-S2_CFGS = _geom(lambda r: r.family == L.TILE_S2)
-T2_CFGS = _geom(lambda r: r.family in (L.TILE_T2, L.TILE_T2_ONE))
-# (the 7x7 window tiles are offered to the tile search unless V2V_S7_PATCH=0)
-S7_CFGS = _geom(lambda r: r.family == L.TILE_S7)
-ABLATION_TILES = _geom(lambda r: r.flags & L.TILE_ABLATION)     # never auto-selected
-# paired launches the engine searches: the library also pairs the ablation instances, the engine never offers them
-PAIR_TILES = tuple(t for t, r in sorted(_TILES.items()) if r.flags & L.TILE_GROUPED and not r.flags & L.TILE_ABLATION)
-# backward-data as a "full" (pad 2) 3x3 convolution: same rule
-BWD_PATCH_TILES = tuple(t for t, r in sorted(_TILES.items()) if r.flags & L.TILE_PAD2 and not r.flags & L.TILE_ABLATION)
-ONE_TILES = tuple(t for t, r in sorted(_TILES.items()) if r.family == L.TILE_ONE)
-PERSISTENT_TILES = ONE_TILES + tuple(t for t, r in sorted(_TILES.items()) if r.family == L.TILE_T2_ONE)    # ONE statistics row per workgroup, finalize in the launch at any size
-ONE_FIN = os.environ.get("V2V_ONE_FIN", "1") != "0"             # ... finalize their <= 256 statistics rows in the launch (0: separate bn_finalize launch, for A/B)
-EXP_TILES = tuple(t for t, r in sorted(_TILES.items()) if r.flags & L.TILE_EXPERIMENT)
-if os.environ.get("V2V_EXP_TILES", "0") == "1":
-    PAIR_TILES = PAIR_TILES + EXP_TILES
-# families the frame-wide search treats as "ping-pong" (every LDS-patch schedule after the first patch kernel)
-_PP_FAMILIES = (L.TILE_PP, L.TILE_PP2, L.TILE_PP3, L.TILE_S7, L.TILE_S2, L.TILE_T2, L.TILE_ONE, L.TILE_T2_ONE)
-
-
-def tile_korder(t):
-    """Weight packing a tile id reads: 0 tap-major class matrices (implicit-GEMM tiles, 7x7 kernels), 1 channel-chunk-major (patch
-    kernels, stride-2 patch kernel), 2 the full-tap chunk-major matrix of a transposed layer (conv3x3_t2_kernel)."""
-    return _TILES[t].korder if t in _TILES else 0
-
-
-def is_patch_tile(t):
-    """Tile ids of the LDS-patch kernels that read channel-chunk-major (korder 1) weights."""
-    return tile_korder(t) == 1
-
-
 FUSE_FINALIZE_MAX_PIXELS = 32768   # larger layers leave thousands of statistics rows: parallel two-stage finalize instead
 PREFETCH_DIST = 12          # K chunks (128 B of every weight row each) the helper wave runs ahead
-
-
-def _cfg3(v):
-    """tile_override / _tuned values: tile id, or (tile, splitk, prefetch)."""
-    if isinstance(v, (tuple, list)):
-        return int(v[0]), int(v[1]), int(v[2])
-    return int(v), 1, 0
 
 
 # Ticket words of one (lane, scratch set): [0, 256) the conv kernels' per-channel-tile arrive / depart tickets, [256, 256 + 64 * 128)
@@ -594,7 +545,8 @@ class Engine:
         if os.environ.get("V2V_PAIR_TILE"):
             self.pair_override = tuple(int(v) for v in os.environ["V2V_PAIR_TILE"].split(","))
         self.lanes_enabled = False   # set by the frame plan: emit independent towers / branches on parallel lanes
-        self._thrash = None
+        self._thrash = None          # 384 MB the tile searches clear in front of every timed launch (_time_launch)
+        self.pair_tune_log = {}      # pair key -> [(us, tile, splitk)] of its search, fastest first (experiments read it)
         # Round 6: weight-gradient launches of a backward pass go to a SIDE stream (autograd.ConvFn.backward).  dW is a leaf of
         # the backward graph -- nothing downstream of a layer's backward needs it before the optimizer step -- while the chain
         # norm-backward -> backward-data -> next layer is strictly serial and leaves the chip idle between its ~4000 dependent
@@ -937,7 +889,7 @@ class Engine:
             fin_counter = self._fin_counters.get(key)
             if fin_counter is None:
                 fin_counter = self._fin_counters[key] = torch.zeros(FIN_COUNTER_WORDS, dtype=torch.int32, device=self.device)
-            fn = L.OneHotNorm()
+            fn = L.OneHotNorm()          # (not _attach_finalize: another struct -- v2v_onehot_norm, no fin_ prefix -- and ticket words of its own)
             fn.counter = fin_counter.data_ptr() + 4 * FIN_ONEHOT_OFFSET  # own region: clear of the conv kernels' per-tile tickets (0..255) AND of the two-level finalize's row-group tickets (256 .. 256 + 64*128)
             fn.gamma = None if gamma is None else gamma.data_ptr()
             fn.beta = None if beta is None else beta.data_ptr()
@@ -979,26 +931,16 @@ class Engine:
         else:
             OH = (H + 2 * pad - pc.KH) // pc.stride + 1
             OW = (W + 2 * pad - pc.KW) // pc.stride + 1
-        d = ConvDesc()
-        d.in_ = x.t.data_ptr(); d.w = pc.buf.data_ptr(); d.w_korder = 0
-        d.zero_page = self.zero_page().data_ptr()
-        self._keep(self._zero_page)
-        d.bias = None if pc.bias is None else pc.bias.data_ptr()
-        d.N, d.H, d.W = N, H, W
-        d.cin, d.cin_stride, d.cout = pc.cin, x.Cs, pc.cout
-        d.KH, d.KW, d.stride, d.pad, d.pad_mode = pc.KH, pc.KW, pc.stride, pad, pad_mode
-        d.transposed = int(pc.transposed)
-        d.OH, d.OW = OH, OW
+        d = self._desc_common(x, pc, pad, pad_mode, OH, OW)
         # raw_act_ok (conv_group -> norm_apply only): the raw tensor may be stored in the activation dtype.  Never on the autograd
         # path (the backward kernels read fp32 raw), never for the 7x7 layers (tiles 60 / 61 and the gather-sum stems write fp32)
         raw_ok_t = bool(raw_act_ok and out_mode == L.OUT_RAW_F32_NHWC and self.dtype == L.BF16 and out is None
                         and pc.KH != 7 and not torch.is_grad_enabled())
         raw_t = raw_ok_t and self.raw_bf16
-        d.dtype, d.out_mode, d.act = self.dtype, (L.OUT_RAW_ACT_NHWC if raw_t else out_mode), act
+        d.out_mode, d.act = (L.OUT_RAW_ACT_NHWC if raw_t else out_mode), act
         d.act_param, d.out_scale = act_param, out_scale
         if act_b is not None:          # (first channel, activation, parameter, scale) of the second head of a merged pair
             d.act_split, d.act_b, d.act_param_b, d.out_scale_b = act_b
-        d.ablate = self.ablate
         d.tile, d.splitk, d.prefetch = _cfg3(self.tile_override.get((pc.cin, pc.cout, pc.KH, pc.stride, int(pc.transposed)), 0))
         tune_key = (pc.cin, pc.cout, pc.KH, pc.stride, int(pc.transposed), N, H, W, out_mode, x.Cs)
         if d.tile == 0 and tune_key in self._tuned:
@@ -1015,11 +957,11 @@ class Engine:
             # from bf16 only -- fall back to the library's default tile instead of failing at launch
             d.tile, d.splitk, d.prefetch = 0, 1, 0
         if act_b is not None:
-            d.tile, d.splitk, d.prefetch = 60, 1, 0          # per-channel epilogues exist in the 7x7 head kernels only
-        if d.tile == 60 and self.rowsum_heads and (pc.cin, pc.cout, pc.KH, pc.stride, int(pc.transposed)) not in self.tile_override \
+            d.tile, d.splitk, d.prefetch = HEAD_TILE, 1, 0   # per-channel epilogues exist in the 7x7 head kernels only
+        if d.tile == HEAD_TILE and self.rowsum_heads and (pc.cin, pc.cout, pc.KH, pc.stride, int(pc.transposed)) not in self.tile_override \
                 and self.dtype == L.BF16 and pc.cout <= 4 and out_mode == L.OUT_F32_NCHW \
                 and x.Cs % 32 == 0 and not want_stats and fin is None:
-            d.tile = 62                                       # conv7x7_rowsum_kernel: the heads as row GEMM + shifted sum (bf16)
+            d.tile = ROWSUM_TILE                              # conv7x7_rowsum_kernel: the heads as row GEMM + shifted sum (bf16)
         if tile_korder(d.tile):
             pc = self._use_korder(d, mod, x.Cs, tile_korder(d.tile))
         else:
@@ -1062,38 +1004,20 @@ class Engine:
             d.stats = st.data_ptr()
             # (not for the 7x7 layers: their halo-patch tiles 60 / 61 have no in-kernel finalize and must stay eligible)
             two_level = bool(fin is not None and N * OH * OW > FUSE_FINALIZE_MAX_PIXELS and self.fused_finalize2 and rows > 512
-                             and pc.KH != 7 and d.tile not in (60, 61))
+                             and pc.KH != 7 and d.tile not in (HEAD_TILE, C8_TILE))
             if fin is not None and N * OH * OW > FUSE_FINALIZE_MAX_PIXELS and not two_level and not (d.tile in PERSISTENT_TILES and ONE_FIN):
                 fin = None             # one workgroup walking >1000 rows costs 0.1-1 ms (profiles/r01_v15_finalize_tail.txt)
                                        # (the persistent tiles leave one row per WORKGROUP, <= 256: they finalize in the launch at any size)
             self.last_finalized = fin is not None
             if fin is not None:
-                norm, ss = fin
-                gamma, beta, eps, mom, rm, rv = self._batchwide_params(norm, N)
-                fin_counter = self._fin_counters.get((self._lane, self._sset))
-                if fin_counter is None:
-                    # [0,128) finalize tickets per channel tile, [128,256) fused-norm departures, [256, 256 + 64 * 128) row-group tickets
-                    fin_counter = self._fin_counters[(self._lane, self._sset)] = torch.zeros(FIN_COUNTER_WORDS, dtype=torch.int32, device=self.device)
-                d.fin_counter = fin_counter.data_ptr()
-                d.fin_gamma = None if gamma is None else gamma.data_ptr()
-                d.fin_beta = None if beta is None else beta.data_ptr()
-                d.fin_scale_shift = ss.data_ptr()
-                d.fin_running_mean = None if rm is None else rm.data_ptr()
-                d.fin_running_var = None if rv is None else rv.data_ptr()
-                d.fin_eps, d.fin_momentum, d.fin_count = eps, mom, N * OH * OW
+                self._attach_finalize(d, fin[0], fin[1], N, N * OH * OW)
                 if two_level:          # round 4: large layers finalize inside the conv launch in two levels (no bn_partial_reduce / bn_finalize launches)
-                    ws = self.scratch("bn_ws", 64 * pc.cout * 2, torch.float64)
-                    d.fin_workspace = ws.data_ptr()
-                for t in (gamma, beta, ss, fin_counter):
-                    if t is not None:
-                        self._keep(t)
+                    d.fin_workspace = self.scratch("bn_ws", 64 * pc.cout * 2, torch.float64).data_ptr()
         if pc.bias is not None:
             self._keep(pc.bias)
         if (self.autotune and d.tile == 0 and self.plan is None and not self.record_only
                 and not torch.is_grad_enabled()):
-            self._tuned[tune_key] = self._autotune(d, want_stats, pc.cout, mod, x.Cs)
-            self._tune_alts[tune_key] = list(getattr(self, "_last_alts", []))
-            self._tune_wide[tune_key] = list(getattr(self, "_last_wide", []))
+            self._tuned[tune_key], self._tune_alts[tune_key], self._tune_wide[tune_key] = self._autotune(d, want_stats, pc.cout, mod, x.Cs)
             self._save_tune_cache()
             d.tile, d.splitk, d.prefetch = self._tuned[tune_key]
             pc = self._use_korder(d, mod, x.Cs, tile_korder(d.tile))
@@ -1117,6 +1041,56 @@ class Engine:
                                   prefetch=int(d.prefetch), convs=2 if act_b is not None else 1))    # merged heads: two reference layers
         return out, rows, (N, OH, OW)
 
+    def _desc_common(self, x, pc, pad, pad_mode, OH, OW):
+        """What every conv descriptor says: operands, geometry (that of packing `pc`), no split-K; raw fp32 NHWC output without
+        activation until the caller says otherwise."""
+        d = ConvDesc()
+        d.in_ = x.t.data_ptr(); d.w = pc.buf.data_ptr(); d.w_korder = pc.korder
+        d.zero_page = self.zero_page().data_ptr()
+        self._keep(self._zero_page)
+        d.bias = None if pc.bias is None else pc.bias.data_ptr()
+        d.N, d.H, d.W = x.N, x.H, x.W
+        d.cin, d.cin_stride, d.cout = pc.cin, x.Cs, pc.cout
+        d.KH, d.KW, d.stride, d.pad, d.pad_mode = pc.KH, pc.KW, pc.stride, pad, pad_mode
+        d.transposed = int(pc.transposed)
+        d.OH, d.OW = OH, OW
+        d.dtype, d.out_mode, d.act = self.dtype, L.OUT_RAW_F32_NHWC, L.ACT_NONE
+        d.act_param, d.out_scale = 0.0, 1.0
+        d.ablate = self.ablate
+        return d
+
+    def _attach_finalize(self, d, norm, ss, N, count):
+        """The launch finalizes its statistics over `count` pixels itself (last-arriving workgroup): `ss` receives [4][C] scale /
+        shift / mean / invstd of training-mode `norm`.  The ticket words are one buffer per (lane, scratch set)."""
+        gamma, beta, eps, mom, rm, rv = self._batchwide_params(norm, N)
+        key = (self._lane, self._sset)
+        fin_counter = self._fin_counters.get(key)
+        if fin_counter is None:
+            fin_counter = self._fin_counters[key] = torch.zeros(FIN_COUNTER_WORDS, dtype=torch.int32, device=self.device)
+        d.fin_counter = fin_counter.data_ptr()
+        d.fin_gamma = None if gamma is None else gamma.data_ptr()
+        d.fin_beta = None if beta is None else beta.data_ptr()
+        d.fin_scale_shift = ss.data_ptr()
+        d.fin_running_mean = None if rm is None else rm.data_ptr()
+        d.fin_running_var = None if rv is None else rv.data_ptr()
+        d.fin_eps, d.fin_momentum, d.fin_count = eps, mom, count
+        for t in (gamma, beta, ss, fin_counter):
+            if t is not None:
+                self._keep(t)
+
+    def _bn_finalize(self, rows, cout, count, norm, ss, N, label):
+        """The statistics rows a conv launch left in the "stats" scratch -> `ss`, as a launch of its own (two-stage above 512 rows)."""
+        gamma, beta, eps, mom, rm, rv = self._batchwide_params(norm, N)
+        st = self.scratch("stats", rows * cout * 2)
+        for t in (gamma, beta):
+            if t is not None:
+                self._keep(t)
+        groups = lib.v2v_bn_finalize_groups(rows)
+        ws = self.scratch("bn_ws", groups * cout * 2, torch.float64) if groups > 0 else None
+        check(lib.v2v_bn_finalize(_ptr(st), rows, cout, count, _ptr(gamma), _ptr(beta), eps,
+                                  _ptr(ss), _ptr(rm), _ptr(rv), mom, _ptr(ws), _stream()), "bn_finalize " + label)
+        self.label(label + ".norm")
+
     # ---------------- paired launches (twin chains) ----------------
     def pair_eligible(self, xa, ma, xb, mb):
         """Can two 3x3 / stride 1 / pad 1 convolutions run as ONE v2v_conv2d_pair launch?  Identical geometry, channel
@@ -1133,21 +1107,11 @@ class Engine:
         """Descriptor of one member of a paired launch: raw fp32 NHWC output + statistics (+ in-kernel finalize) on the
         CURRENT scratch sub-set.  fused = (act, act_param, res0, res1, y): the norm, activation and residual adds run in
         the conv kernel (V2V_OUT_NORM_ACT_NHWC) and `y` (an Act) receives the result; no raw tensor."""
-        pc = self._use_korder1_pc(mod, x.Cs)
+        pc = self.packed(mod, x.Cs, korder=1, refresh=False)       # the channel-chunk-major packing every pair tile reads
+        if self.plan is None:
+            pc.refresh()
         N, H, W = x.N, x.H, x.W
-        d = ConvDesc()
-        d.in_ = x.t.data_ptr(); d.w = pc.buf.data_ptr(); d.w_korder = 1
-        d.zero_page = self.zero_page().data_ptr()
-        self._keep(self._zero_page)
-        d.bias = None if pc.bias is None else pc.bias.data_ptr()
-        d.N, d.H, d.W = N, H, W
-        d.cin, d.cin_stride, d.cout = pc.cin, x.Cs, pc.cout
-        d.KH, d.KW, d.stride, d.pad, d.pad_mode = 3, 3, 1, pad, pad_mode
-        d.transposed = 0
-        d.OH, d.OW = H, W
-        d.dtype, d.out_mode, d.act = self.dtype, L.OUT_RAW_F32_NHWC, L.ACT_NONE
-        d.act_param, d.out_scale = 0.0, 1.0
-        d.ablate = self.ablate
+        d = self._desc_common(x, pc, pad, pad_mode, H, W)         # (pair_eligible: 3x3 / stride 1 Conv2d)
         d.tile, d.splitk, d.prefetch = tile3
         if pc.cin != x.C:
             raise RuntimeError("conv %s: input has %d channels, layer expects %d" % (label, x.C, pc.cin))
@@ -1175,34 +1139,13 @@ class Engine:
             d.stats = self.scratch("stats", rows * pc.cout * 2).data_ptr()
         finalized = fin is not None and (fused is not None or N * H * W <= FUSE_FINALIZE_MAX_PIXELS)
         if finalized:
-            norm, ss = fin
-            gamma, beta, eps, mom, rm, rv = self._batchwide_params(norm, N)
-            key = (self._lane, self._sset)
-            fin_counter = self._fin_counters.get(key)
-            if fin_counter is None:
-                fin_counter = self._fin_counters[key] = torch.zeros(FIN_COUNTER_WORDS, dtype=torch.int32, device=self.device)
-            d.fin_counter = fin_counter.data_ptr()
-            d.fin_gamma = None if gamma is None else gamma.data_ptr()
-            d.fin_beta = None if beta is None else beta.data_ptr()
-            d.fin_scale_shift = ss.data_ptr()
-            d.fin_running_mean = None if rm is None else rm.data_ptr()
-            d.fin_running_var = None if rv is None else rv.data_ptr()
-            d.fin_eps, d.fin_momentum, d.fin_count = eps, mom, N * H * W
-            for t in (gamma, beta, ss, fin_counter):
-                if t is not None:
-                    self._keep(t)
+            self._attach_finalize(d, fin[0], fin[1], N, N * H * W)
         if pc.bias is not None:
             self._keep(pc.bias)
         if not self._splitk_workspace(d):
             raise RuntimeError("conv pair %s: split-K %d does not fit this layer" % (label, tile3[1]))
         self._keep(pc.buf)
         return d, raw, rows, finalized, pc
-
-    def _use_korder1_pc(self, mod, cin_stride):
-        pc = self.packed(mod, cin_stride, korder=1, refresh=False)
-        if self.plan is None:
-            pc.refresh()
-        return pc
 
     def fused_norm_fits(self, tile3, N, H, W, cout, members=2):
         """V2V_OUT_NORM_ACT_NHWC (include/v2v_hip.h, "fused norm"): single-phase tiles, no split-K, every workgroup of the
@@ -1287,7 +1230,7 @@ class Engine:
             tile3 = self._tuned[key] = self._autotune_pair(xa, ma, xb, mb, pad_mode, pad, fins, key, fuse=fuse)
             self._save_tune_cache()
         else:
-            tile3 = (80 if W % 64 else 83, 1, 0)
+            tile3 = (TS.default_pair_tile(W), 1, 0)
         fa = fb = None
         if fuse is not None and fins[0] is not None and self.fused_norm_fits(tile3, N, H, W, ma.out_channels):
             act, act_param, adds_a, adds_b, ya, yb = fuse
@@ -1305,51 +1248,33 @@ class Engine:
         return ((rawa, rowsa, fina), (rawb, rowsb, finb)), (N, H, W)
 
     def _autotune_pair(self, xa, ma, xb, mb, pad_mode, pad, fins, key, reps=7, fuse=None):
-        """Measured choice of (tile, split-K) for a paired launch: every second-schedule ping-pong tile, unsplit and
-        split 2 (cold weights: a 384 MB memset between launches, as _autotune)."""
-        ncc = xa.Cs // (64 if self.dtype == L.BF16 else 32)
-        if self._thrash is None:
-            self._thrash = torch.empty(96 << 20, dtype=torch.float32, device=self.device)
+        """Measured choice of (tile, split-K) for a paired launch among tile_search.pair_candidates (cold weights, as _autotune)."""
         st = _stream()
         best, best_ms, alts = None, float("inf"), []
-        for t in PAIR_TILES:
-            th, tw, bn = PATCH_CFGS[t]
-            tiles = xa.N * -(-xa.H // th) * -(-xa.W // tw) * -(-ma.out_channels // bn)
-            for S in (1, 2):
-                if S > 1 and (ncc < 2 * S or tiles * S * 2 > 1024):
-                    continue
-                fa = fb = None
-                if fuse is not None and fins[0] is not None and self.fused_norm_fits((t, S, 0), xa.N, xa.H, xa.W, ma.out_channels):
-                    act, act_param, adds_a, adds_b, ya, yb = fuse         # timed as it will run: norm / act / adds in the launch
-                    fa, fb = (act, act_param, adds_a[0], adds_a[1], ya), (act, act_param, adds_b[0], adds_b[1], yb)
-                try:
-                    da = self._pair_desc(xa, ma, pad_mode, pad, (t, S, 0), fins[0], "tune", fused=fa)[0]
-                    with self.scratch_set(1):
-                        db = self._pair_desc(xb, mb, pad_mode, pad, (t, S, 0), fins[1], "tune", fused=fb)[0]
-                except RuntimeError:
-                    continue
-                if lib.v2v_conv2d_pair(C.byref(da), C.byref(db), st) != 0:
-                    continue
-                e0 = [torch.cuda.Event(enable_timing=True) for _ in range(reps)]
-                e1 = [torch.cuda.Event(enable_timing=True) for _ in range(reps)]
-                for r in range(reps):
-                    self._thrash.zero_()
-                    e0[r].record()
-                    lib.v2v_conv2d_pair(C.byref(da), C.byref(db), st)
-                    e1[r].record()
-                e1[-1].synchronize()
-                ms = sorted(a.elapsed_time(b) for a, b in zip(e0, e1))[reps // 2]
-                if fuse is not None and fa is None:
-                    ms += 0.012                  # the bn_apply_pair launch the unfused variant still needs (~6 us + its gap)
-                alts.append((ms, (t, S, 0)))
-                if ms < best_ms:
-                    best, best_ms = (t, S, 0), ms
+        for t, S, _ in TS.pair_candidates(xa.N, xa.H, xa.W, xa.Cs, ma.out_channels, self.dtype):
+            fa = fb = None
+            if fuse is not None and fins[0] is not None and self.fused_norm_fits((t, S, 0), xa.N, xa.H, xa.W, ma.out_channels):
+                act, act_param, adds_a, adds_b, ya, yb = fuse         # timed as it will run: norm / act / adds in the launch
+                fa, fb = (act, act_param, adds_a[0], adds_a[1], ya), (act, act_param, adds_b[0], adds_b[1], yb)
+            try:
+                da = self._pair_desc(xa, ma, pad_mode, pad, (t, S, 0), fins[0], "tune", fused=fa)[0]
+                with self.scratch_set(1):
+                    db = self._pair_desc(xb, mb, pad_mode, pad, (t, S, 0), fins[1], "tune", fused=fb)[0]
+            except RuntimeError:
+                continue
+            ms = self._time_launch(lambda: lib.v2v_conv2d_pair(C.byref(da), C.byref(db), st), reps)
+            if ms is None:
+                continue
+            if fuse is not None and fa is None:
+                ms += 0.012                  # the bn_apply_pair launch the unfused variant still needs (~6 us + its gap)
+            alts.append((ms, (t, S, 0)))
+            if ms < best_ms:
+                best, best_ms = (t, S, 0), ms
         if best is None:
             raise RuntimeError("no paired-launch tile fits this layer")
         alts.sort()
         self._tune_alts[key] = [c for _, c in alts if c != best][:5]
         self._tune_wide[key] = []
-        self.pair_tune_log = getattr(self, "pair_tune_log", {})
         self.pair_tune_log[key] = [(round(ms * 1e3, 1), c[0], c[1]) for ms, c in alts]
         return best
 
@@ -1382,16 +1307,7 @@ class Engine:
         for (raw, rows, fin), norm, ss, k, lbl in ((ra, norma, ssa, 0, labels[0]), (rb, normb, ssb, 1, labels[1])):
             if not fin:                                       # large layers: parallel two-stage finalize per member
                 with self.scratch_set(k):
-                    gamma, beta, eps, mom, rm, rv = self._batchwide_params(norm, N)
-                    st = self.scratch("stats", rows * cout * 2)
-                    for t in (gamma, beta):
-                        if t is not None:
-                            self._keep(t)
-                    groups = lib.v2v_bn_finalize_groups(rows)
-                    ws = self.scratch("bn_ws", groups * cout * 2, torch.float64) if groups > 0 else None
-                    check(lib.v2v_bn_finalize(_ptr(st), rows, cout, N * OH * OW, _ptr(gamma), _ptr(beta), eps,
-                                              _ptr(ss), _ptr(rm), _ptr(rv), mom, _ptr(ws), _stream()), "bn_finalize " + lbl)
-                    self.label(lbl + ".norm")
+                    self._bn_finalize(rows, cout, N * OH * OW, norm, ss, N, lbl)
         a0, a1 = adds_a
         b0, b1 = adds_b
         xa3, xb3 = self._x3_out(ya), self._x3_out(yb)
@@ -1442,33 +1358,29 @@ class Engine:
         keyed separately (leading -1) in the same tuning table.  Measured only while `autotune` is on (the first
         training steps of bench.py --mode train); later steps replay the selection."""
         key = (-1, d.cin, d.cout, d.KH, d.stride, d.transposed, d.N, d.H, d.W, d.cin_stride, d.cout_stride, d.pad)
-        forced = self.bwd_tile_override.get((d.cin, d.cout, d.KH, d.stride, int(d.transposed)))
-        if forced is not None:                       # tests: a given tile for the backward-data operator (dY channels, dX channels, k, stride, transposed)
-            d.tile, d.splitk, d.prefetch = _cfg3(forced)
+
+        def use(cfg):                                # configuration, the packing its tile reads, its split-K workspace
+            d.tile, d.splitk, d.prefetch = cfg
             if conv is not None:
                 self._use_korder(d, conv, d.cin_stride, tile_korder(d.tile), role="bwd", reflect=reflect)
-            if not self._splitk_workspace(d):
+            return self._splitk_workspace(d)
+
+        forced = self.bwd_tile_override.get((d.cin, d.cout, d.KH, d.stride, int(d.transposed)))
+        if forced is not None:                       # tests: a given tile for the backward-data operator (dY channels, dX channels, k, stride, transposed)
+            if not use(_cfg3(forced)):
                 raise RuntimeError("bwd_tile_override: split-K workspace")
             return
         if key not in self._tuned:
             if not (self.autotune and self.plan is None and not self.record_only):
-                d.tile, d.splitk, d.prefetch = 0, 0, 0
-                if conv is not None:
-                    self._use_korder(d, conv, d.cin_stride, 0, role="bwd", reflect=reflect)
-                self._splitk_workspace(d)
+                use((0, 0, 0))
                 return
             # conv given: the patch kernels are candidates too -- backward-data of a stride-2 Conv2d is a transposed stride-2 convolution
             # (conv3x3_t2_kernel), that of a ConvTranspose2d a stride-2 convolution (conv3x3_s2_kernel), on the role-swapped packings
-            self._tuned[key] = self._autotune(d, False, dx_channels, mod=conv, cin_stride=d.cin_stride, role="bwd", reflect=reflect)
+            self._tuned[key], self._tune_alts[key], self._tune_wide[key] = self._autotune(
+                d, False, dx_channels, mod=conv, cin_stride=d.cin_stride, role="bwd", reflect=reflect)
             self._save_tune_cache()
-        d.tile, d.splitk, d.prefetch = _cfg3(self._tuned[key])
-        if conv is not None:
-            self._use_korder(d, conv, d.cin_stride, tile_korder(d.tile), role="bwd", reflect=reflect)
-        if not self._splitk_workspace(d):
-            d.tile, d.splitk, d.prefetch = 0, 0, 0
-            if conv is not None:
-                self._use_korder(d, conv, d.cin_stride, 0, role="bwd", reflect=reflect)
-            self._splitk_workspace(d)
+        if not use(_cfg3(self._tuned[key])):
+            use((0, 0, 0))
 
     def log_backward(self, kind, label, conv, cin, cout, N, pixels):
         """Algorithmic FLOP of a backward launch (same count as its forward conv), for bench.py's training roofline."""
@@ -1491,45 +1403,20 @@ class Engine:
         with open(self._tune_cache_path, "w") as f:
             json.dump(data, f)
 
-    def _use_korder1(self, d, mod, cin_stride):
-        """Point the descriptor at the channel-chunk-major packing of `mod` (patch-kernel tile ids >= 32)."""
-        pc = self.packed(mod, cin_stride, korder=1)
-        d.w, d.w_korder = pc.buf.data_ptr(), 1
-        return pc
-
-    def bwd_patch_eligible(self, d, mod):
-        """Backward-data of a 3x3 / stride 1 Conv2d on the single-phase 3x3 tiles (round 6): the operator IS a 3x3 convolution of the
-        output gradient with the role-swapped, tap-flipped weights (PackedConv korder 4) and pad 2 - p -- behind a ReflectionPad2d
-        (p = 0) a "full" convolution onto the padded grid, which reflect_pad_fold then folds.  The generic tiles ran these at
-        62 us for the 1024 -> 1024 layers (the forward, same FLOP, takes 44 on tile 90: profiles/r06_v17_train_by_grid.txt)."""
-        bke = 64 if self.dtype == L.BF16 else 32
-        return (isinstance(mod, nn.Conv2d) and tuple(mod.kernel_size) == (3, 3) and tuple(mod.stride) == (1, 1) and mod.groups == 1
-                and d.cin_stride % bke == 0 and d.out_mode == L.OUT_ACT_NHWC and os.environ.get("V2V_BWD_PATCH", "1") != "0")
-
-    def bwd_c8_eligible(self, d, mod):
-        """Backward-data of the 7x7 heads (ngf -> 3 behind ReflectionPad2d(3): models/networks.py:178-183) on conv7x7_c8_kernel
-        (tile 61): the output gradient is ONE 16-byte vector per pixel, the operator a 7x7 convolution of it with the role-swapped,
-        tap-flipped weights (PackedConv korder 5) and zero padding 6 - p.  The generic tiles walk it in 128-byte K chunks that are
-        7/8 padding: 816 us per head at 2048x1024 (profiles/r06_v14_train_hires_by_grid.txt)."""
-        vec = 8 if self.dtype == L.BF16 else 4
-        return (isinstance(mod, nn.Conv2d) and tuple(mod.kernel_size) == (7, 7) and tuple(mod.stride) == (1, 1) and mod.groups == 1
-                and d.cin_stride == vec and mod.in_channels <= 128 and mod.in_channels % vec == 0 and d.cout_stride % vec == 0
-                and d.out_mode == L.OUT_ACT_NHWC and os.environ.get("V2V_BWD_C8", "1") != "0")
-
     def _use_korder(self, d, mod, cin_stride, korder, role="fwd", reflect=False):
-        if role == "bwd" and d.tile == 61:
-            if not self.bwd_c8_eligible(d, mod):
+        if role == "bwd" and d.tile == C8_TILE:
+            if not TS.bwd_c8_eligible(d, self.dtype, mod):
                 raise ValueError("tile 61 as a backward-data operator: a 7x7 / stride 1 Conv2d whose output gradient is one 16-byte vector per pixel")
             pc = self.packed(mod, cin_stride, role="bwd", reflect=reflect, korder=5)
             d.transposed, d.pad = 0, pc.KH - 1 - pc.pad
             d.w, d.w_korder = pc.buf.data_ptr(), 0
             return pc
-        if role == "bwd" and korder == 1 and _flag(d.tile, L.TILE_PAD2) and self.bwd_patch_eligible(d, mod):
+        if role == "bwd" and korder == 1 and _flag(d.tile, L.TILE_PAD2) and TS.bwd_patch_eligible(d, self.dtype, mod):
             pc = self.packed(mod, cin_stride, role="bwd", reflect=reflect, korder=4)
             d.transposed, d.pad = 0, pc.KH - 1 - pc.pad
             d.w, d.w_korder = pc.buf.data_ptr(), 1
             return pc
-        if d.tile in PERSISTENT_TILES and cin_stride == 32 and role == "fwd" and (self.pairx_eligible(d) or self.pairx_t_eligible(d)):
+        if d.tile in PERSISTENT_TILES and cin_stride == 32 and role == "fwd" and (TS.pairx_eligible(d, self.dtype) or TS.pairx_t_eligible(d, self.dtype)):
             # 64-byte pixels on the persistent single-chunk tiles: paired-x packing (PairedXConv).  Gated on the view's own
             # eligibility (ADVICE r5; round 6: an fp32 engine's 32-channel layers -- one 128-byte chunk, patch-eligible, so the
             # persistent tiles are among the candidates -- took this branch and PairedXConv raised for FlowNet2's 64 -> 32
@@ -1540,48 +1427,6 @@ class Engine:
         if role == "bwd":
             d.transposed, d.pad = int(pc.transposed), pc.pad      # (a previous candidate may have been the convolution form above)
         return pc
-
-    def _use_korder0(self, d, mod, cin_stride):
-        pc = self.packed(mod, cin_stride, korder=0)
-        d.w, d.w_korder = pc.buf.data_ptr(), 0
-        return pc
-
-    def patch_eligible(self, d):
-        bke = 64 if self.dtype == L.BF16 else 32
-        return (not d.transposed and d.KH == 3 and d.KW == 3 and d.stride == 1 and d.pad == 1
-                and d.cin_stride % bke == 0)
-
-    def pairx_eligible(self, d):
-        """Persistent single-chunk tiles 140 / 141 (/ 143) on a layer with 64-byte pixels (<= 32 -> 32 channels, bf16, raw fp32 output): the
-        paired-x view (PairedXConv) -- pairs of pixels as one 128-byte pixel of a 64 -> 64 layer."""
-        return (self.dtype == L.BF16 and not d.transposed and d.KH == 3 and d.KW == 3 and d.stride == 1 and d.pad == 1
-                and d.cin_stride == 32 and d.cout == 32 and d.out_mode in (L.OUT_RAW_F32_NHWC, L.OUT_RAW_ACT_NHWC) and d.W % 2 == 0 and (d.W // 2) % 32 == 0
-                and d.H % 8 == 0 and os.environ.get("V2V_PAIRX", "1") != "0")
-
-    def pairx_t_eligible(self, d):
-        """Persistent transposed tile 114 on a layer with 64-byte pixels (<= 32 -> 16 channels): the paired-x view (PairedXConvT)."""
-        return (self.dtype == L.BF16 and bool(d.transposed) and d.KH == 3 and d.KW == 3 and d.stride == 2 and d.pad == 1
-                and d.cin_stride == 32 and d.cout == 16 and d.out_mode in (L.OUT_RAW_F32_NHWC, L.OUT_RAW_ACT_NHWC) and d.W % 2 == 0 and (d.W // 2) % 32 == 0
-                and d.H % 8 == 0 and d.OH == 2 * d.H and d.OW == 2 * d.W and os.environ.get("V2V_PAIRX", "1") != "0")
-
-    def s7_eligible(self, d):
-        """7x7-window tiles 120 / 121: dense bf16 7x7 / stride 1 / pad 3 Conv2d whose channel stride is a whole number of 128-byte chunks
-        (the stems on the pooled label encodings, edge2face's 45 -> 128 stem).  Round 5: validated on three boxes (parity test, 1.1-1.7x on
-        the 64 / 128-channel stems: profiles/r05_v1_stem7_bench.txt) -- ON by default, V2V_S7_PATCH=0 takes them out of the search."""
-        return (self.dtype == L.BF16 and not d.transposed and d.KH == 7 and d.KW == 7 and d.stride == 1 and d.pad == 3
-                and d.cin_stride % 64 == 0 and d.out_mode != L.OUT_NORM_ACT_NHWC and os.environ.get("V2V_S7_PATCH", "1") != "0")
-
-    def s2_eligible(self, d):
-        """conv3x3_s2_kernel: 3x3 / stride 2 / zero pad 1 Conv2d whose channel stride is a whole 128-byte chunk."""
-        bke = 64 if self.dtype == L.BF16 else 32
-        return (not d.transposed and d.KH == 3 and d.KW == 3 and d.stride == 2 and d.pad == 1 and d.pad_mode == L.PAD_ZERO
-                and d.cin_stride % bke == 0 and d.out_mode != L.OUT_NORM_ACT_NHWC and os.environ.get("V2V_S2_PATCH", "1") != "0")
-
-    def t2_eligible(self, d):
-        """conv3x3_t2_kernel: ConvTranspose2d(3x3, stride 2, padding 1) whose channel stride is a whole 128-byte chunk."""
-        bke = 64 if self.dtype == L.BF16 else 32
-        return (bool(d.transposed) and d.KH == 3 and d.KW == 3 and d.stride == 2 and d.pad == 1
-                and d.cin_stride % bke == 0 and d.out_mode != L.OUT_NORM_ACT_NHWC and os.environ.get("V2V_T2_PATCH", "1") != "0")
 
     def _splitk_workspace(self, d):
         """Attach the split-K slab scratch and ticket words to a descriptor (no-op for splitk <= 1)."""
@@ -1604,143 +1449,61 @@ class Engine:
         self._keep(skc)
         return True
 
-    def _autotune(self, d, want_stats, cout, mod=None, cin_stride=0, reps=5, role="fwd", reflect=False):
-        """Time every (tile, split-K, weight-prefetch) configuration that fits this launch; returns the fastest
-        triple.  Runs once per conv shape while a frame plan is being built, never inside a timed region.  Each
-        timed launch is preceded by a 384 MB memset: at batch 1 a frame streams ~0.8 GB of weights, so every layer
-        meets its weights COLD in L2 / Infinity Cache -- back-to-back warm launches favour shallow LDS-DMA rings
-        and no prefetch, which stall on real frames."""
-        M = d.N * (d.H * d.W if d.transposed else d.OH * d.OW)
-        ncls = 4 if (d.transposed and d.stride == 2) else 1
-        nk = (d.KH * d.KW * d.cin_stride * (2 if self.dtype == L.BF16 else 4)) // 128 // ncls
-        cands = []
-        for t, (bm, bn, helper) in sorted(TILE_CFGS.items()):
-            if t == 4 and cout > 32:
-                continue
-            tiles = -(-M // (bm * ncls)) * -(-cout // bn) * ncls
-            for S in (1, 2, 3, 4, 6, 8):
-                if S > 1 and (tiles * S > 1024 or nk // S < 4):
-                    continue
-                if S == 1 and t >= 18 and tiles < 96:
-                    continue            # large tiles that cannot fill the chip without split-K
-                cands.append((t, S, 0))      # (prefetch-helper variants never won a sweep: not searched)
-        bke_ = 32 if self.dtype == L.BF16 else 16         # whole 64-byte half chunks (conv7x7_head_kernel, HC = 1)
-        if (not d.transposed and d.KH == 7 and d.KW == 7 and d.stride == 1 and d.pad == 3 and cout <= 32
-                and d.cin_stride % bke_ == 0 and not d.fin_counter
-                and (d.out_mode == L.OUT_F32_NCHW or d.out_mode == L.OUT_RAW_F32_NHWC)):
-            cands.append((60, 1, 0))          # conv7x7_head_kernel (LDS patch + 16-wide MFMA)
-            if (self.rowsum_heads and self.dtype == L.BF16 and cout <= 4 and d.out_mode == L.OUT_F32_NCHW and d.cin_stride % 32 == 0
-                    and not d.stats):
-                cands.append((62, 1, 0))      # conv7x7_rowsum_kernel (row GEMM + shifted sum)
-        if (not d.transposed and d.KH == 7 and d.KW == 7 and d.stride == 1 and d.pad == 3 and cout <= 128
-                and d.cin_stride * (2 if self.dtype == L.BF16 else 4) == 16 and not d.fin_counter
-                and (d.out_mode == L.OUT_F32_NCHW or d.out_mode == L.OUT_RAW_F32_NHWC)):
-            cands.append((61, 1, 0))          # conv7x7_c8_kernel: 16-byte pixels (the 6-channel previous-frame stems), four taps per MFMA step
-        if mod is not None and role == "fwd" and self.patch_eligible(d):
-            ncc = d.cin_stride // (64 if self.dtype == L.BF16 else 32)
-            for t, (th, tw, bn) in sorted(PATCH_CFGS.items()):
-                if t in EXP_TILES and os.environ.get("V2V_EXP_TILES", "0") != "1":
-                    continue
-                if tw == 64 and d.OW % 64 != 0 and d.OW > 32:
-                    pass                      # ragged tiles are legal, just wasteful; let the timing decide
-                tiles = d.N * -(-d.OH // th) * -(-d.OW // tw) * -(-cout // bn)
-                for S in (1, 2, 3, 4, 8):
-                    if S > 1 and (tiles * S > 1024 or ncc < S):
-                        continue
-                    if S == 1 and tiles < 64:
-                        continue
-                    cands.append((t, S, 0))
-        if mod is not None and role == "bwd" and self.bwd_c8_eligible(d, mod):
-            cands.append((61, 1, 0))          # conv7x7_c8_kernel on the tap-flipped role-swapped weights (full convolution of the head's output gradient)
-        if mod is not None and role == "bwd" and self.bwd_patch_eligible(d, mod):
-            for t in BWD_PATCH_TILES:
-                th, tw, bn = PATCH_CFGS[t]
-                tiles = d.N * -(-d.OH // th) * -(-d.OW // tw) * -(-cout // bn)
-                ncc = d.cin_stride // (64 if self.dtype == L.BF16 else 32)
-                for S in (1, 2):
-                    if (S > 1 and (tiles * S > 1024 or ncc < S)) or (S == 1 and tiles < 64):
-                        continue
-                    cands.append((t, S, 0))
-        if mod is not None and role == "fwd" and self.pairx_eligible(d) and d.N * (d.H // 8) * (d.W // 64) >= 64:
-            for t in ONE_TILES:
-                if t not in EXP_TILES or os.environ.get("V2V_EXP_TILES", "0") == "1":
-                    cands.append((t, 1, 0))
-        if mod is not None and role == "fwd" and self.pairx_t_eligible(d) and d.N * (d.H // 8) * (d.W // 64) >= 48:
-            cands.append((114, 1, 0))
-        if mod is not None and role == "fwd" and self.s7_eligible(d):
-            for t, (th, tw, bn) in sorted(S7_CFGS.items()):
-                tiles = d.N * -(-d.OH // th) * -(-d.OW // tw) * -(-cout // bn)
-                if tiles >= 64 and (bn <= 64 or cout > 64):
-                    cands.append((t, 1, 0))
-        if mod is not None and self.s2_eligible(d):
-            for t, (th, tw, bn) in sorted(S2_CFGS.items()):
-                tiles = d.N * -(-d.OH // th) * -(-d.OW // tw) * -(-cout // bn)
-                if tiles >= 64:
-                    cands.append((t, 1, 0))
-        if mod is not None and self.t2_eligible(d):
-            for t, (th, tw, bn) in sorted(T2_CFGS.items()):
-                tiles = d.N * -(-((d.OH + 1) // 2) // th) * -(-((d.OW + 1) // 2) // tw) * -(-cout // bn)
-                if tiles >= 48:
-                    cands.append((t, 1, 0))
+    def _autotune(self, d, want_stats, cout, mod=None, cin_stride=0, role="fwd", reflect=False):
+        """Time every (tile, split-K, weight-prefetch) configuration tile_search.conv_candidates lists for this launch; returns
+        (fastest triple, runners-up, wider list: tile_search.runners_up).  Runs once per conv shape while a frame plan is being
+        built, never inside a timed region."""
+        cands = TS.conv_candidates(d, self.dtype, cout, mod, role, self.rowsum_heads)
         st = _stream()
-        if self._thrash is None:
-            self._thrash = torch.empty(96 << 20, dtype=torch.float32, device=self.device)
-        def time_cfg(t, S, pf, reps):
+        def prepare(t, S, pf):
             d.tile, d.splitk, d.prefetch = t, S, pf
             if mod is not None:
                 self._use_korder(d, mod, cin_stride, tile_korder(t), role=role, reflect=reflect)
             if want_stats:
                 rows = lib.v2v_conv_stats_rows(C.byref(d))
                 if rows <= 0:
-                    return None
+                    return False
                 d.stats = self.scratch("stats", rows * cout * 2).data_ptr()
-            if not self._splitk_workspace(d):
-                return None
-            if lib.v2v_conv2d(C.byref(d), st) != 0:
-                return None
-            e0 = [torch.cuda.Event(enable_timing=True) for _ in range(reps)]
-            e1 = [torch.cuda.Event(enable_timing=True) for _ in range(reps)]
-            for r in range(reps):
-                self._thrash.zero_()
-                e0[r].record()
-                lib.v2v_conv2d(C.byref(d), st)
-                e1[r].record()
-            e1[-1].synchronize()
-            return sorted(a.elapsed_time(b) for a, b in zip(e0, e1))[reps // 2]      # median
+            return self._splitk_workspace(d)
 
+        launch = lambda: lib.v2v_conv2d(C.byref(d), st)
         timed = []
-        for t, S, pf in cands:
-            ms = time_cfg(t, S, pf, 3)
+        for cfg in cands:
+            ms = self._time_launch(launch, 3, lambda: prepare(*cfg))
             if ms is not None:
-                timed.append((ms, (t, S, pf)))
+                timed.append((ms, cfg))
         if os.environ.get("V2V_TUNE_DEBUG"):
             print("autotune %s: %d candidates, %d ran; fastest %s; last error: %s" % ((d.cin, d.cout, d.KH, d.stride, d.transposed, d.cout_stride), len(cands), len(timed),
                   sorted(timed)[:3], lib.v2v_last_error().decode()[:200]), file=sys.stderr)
         if not timed:
-            return (0, 1, 0)
+            return (0, 1, 0), [], []
         # second pass over the front-runners with more repetitions: single medians of 3 are noisy enough to flip
         # the choice between runs (181 vs 194 fps observed)
         timed.sort()
         best, best_ms = timed[0][1], float("inf")
         for _, cfg in timed[:6]:
-            ms = time_cfg(cfg[0], cfg[1], cfg[2], 11)
+            ms = self._time_launch(launch, 11, lambda: prepare(*cfg))
             if ms is not None and ms < best_ms:
                 best, best_ms = cfg, ms
-        # runners-up for the whole-frame search of the frame plan (models/vid2vid_model_G._FramePlan._frame_tune): the
-        # fastest few in isolation plus the fastest unsplit ones (split-K fills an idle chip; beside concurrent lanes it
-        # only adds slab traffic)
-        unsplit = [cfg for _, cfg in timed if cfg[1] <= 1]
-        pp_ = lambda t: _TILES[t].family in _PP_FAMILIES
-        alts = ([cfg for _, cfg in timed[:3]] + unsplit[:3]
-                + [cfg for _, cfg in timed if cfg[0] == best[0] and cfg[1] <= 2]          # the winner's tile, less split
-                + [cfg for cfg in unsplit if pp_(cfg[0])][:1])                             # the best unsplit ping-pong tile
-        self._last_alts = [c for i, c in enumerate(alts) if c != best and c not in alts[:i]][:7]
-        # for the heaviest shapes of a frame the whole-frame search also walks every lightly split configuration that was
-        # not hopeless in isolation
-        self._last_wide = ([cfg for ms, cfg in timed if pp_(cfg[0]) and cfg[1] <= 2 and cfg != best]      # every ping-pong tile
-                           + [cfg for ms, cfg in timed if not pp_(cfg[0]) and cfg[1] <= 2 and ms <= 1.7 * timed[0][0]
-                              and cfg != best][:10])
-        return best
+        return (best,) + TS.runners_up(timed, best)
+
+    def _time_launch(self, launch, reps, prepare=None):
+        """Median milliseconds of `reps` runs of launch() (a library call: 0 = launched), None when prepare() or the first launch
+        refuses.  Each timed run follows a 384 MB memset: at batch 1 a frame streams ~0.8 GB of weights, so every layer meets
+        its weights COLD in L2 / Infinity Cache -- back-to-back warm launches favour shallow LDS-DMA rings and no prefetch,
+        which stall on real frames."""
+        if self._thrash is None:
+            self._thrash = torch.empty(96 << 20, dtype=torch.float32, device=self.device)
+        if (prepare is not None and not prepare()) or launch() != 0:
+            return None
+        e0, e1 = ([torch.cuda.Event(enable_timing=True) for _ in range(reps)] for _ in range(2))
+        for r in range(reps):
+            self._thrash.zero_()
+            e0[r].record()
+            launch()
+            e1[r].record()
+        e1[-1].synchronize()
+        return sorted(a.elapsed_time(b) for a, b in zip(e0, e1))[reps // 2]      # median
 
     def _norm_params(self, norm, N):
         """(gamma, beta, eps, momentum, running_mean, running_var) of a training-mode norm layer
@@ -1829,16 +1592,7 @@ class Engine:
         if ss is None:
             ss = self.scratch("scale_shift", 4 * cout)
         if not finalized:
-            gamma, beta, eps, mom, rm, rv = self._batchwide_params(norm, N)
-            st = self.scratch("stats", rows * cout * 2)
-            for t in (gamma, beta):
-                if t is not None:
-                    self._keep(t)
-            groups = lib.v2v_bn_finalize_groups(rows)
-            ws = self.scratch("bn_ws", groups * cout * 2, torch.float64) if groups > 0 else None
-            check(lib.v2v_bn_finalize(_ptr(st), rows, cout, N * OH * OW, _ptr(gamma), _ptr(beta), eps,
-                                      _ptr(ss), _ptr(rm), _ptr(rv), mom, _ptr(ws), _stream()), "bn_finalize " + label)
-            self.label(label + ".norm")
+            self._bn_finalize(rows, cout, N * OH * OW, norm, ss, N, label)
         y = self.empty_act(N, OH, OW, cout)
         y3 = self._x3_out(y)
         if y3 is not None:
