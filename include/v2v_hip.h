@@ -337,13 +337,19 @@ int v2v_bn_apply_pair(const float* raw_a, const float* scale_shift_a, const void
  * dRaw = scale*(g - mean(g) - xhat*mean(g*xhat)), written NHWC in `dtype` with channel stride
  * c_stride_out (pad channels zero).  dy: NHWC `dtype` [P][c_stride]; raw: fp32 [P][c_stride_raw];
  * stats: the [4][C] array of v2v_bn_finalize.  dgamma/dbeta may be NULL.
- * workspace: (v2v_bn_backward_rows(P)*2*C + 2*C) floats. */
+ * workspace: (v2v_bn_backward_rows(P)*2*C + 2*C) floats.  That is an upper bound: with more than 2048 workgroups
+ * (pixel blocks x 64-channel slabs) the launch takes fewer, longer pixel blocks and uses fewer rows, the [2][C]
+ * reduction coefficients right behind the rows it uses (P = 4160, C = 2112: 64 of the 65 rows).
+ * Up to 64 slabs (C <= 4096) the last workgroup of a slab finalizes inside the reduce launch; V2V_BN_BWD_FUSED=0
+ * selects the separate finalize launch (same arithmetic, same bits).  The variable is read ONCE per process, at the
+ * first v2v_bn_backward / v2v_channel_sum call: changing it afterwards has no effect. */
 int v2v_bn_backward_rows(int64_t P);
 int v2v_bn_backward(const void* dy, const float* raw, int32_t c_stride_raw, const float* stats,
                     void* draw, int32_t c_stride_out, float* dgamma, float* dbeta, int32_t accumulate,
                     float* workspace, int64_t P, int32_t C, int32_t c_stride,
                     int32_t act, float act_param, int32_t dtype, void* stream);
-/* out[c] (+)= sum over pixels of x[p][c]  (bias gradients).  workspace: v2v_bn_backward_rows(P)*2*C floats */
+/* out[c] (+)= sum over pixels of x[p][c]  (bias gradients).  workspace: v2v_bn_backward_rows(P)*2*C floats
+ * (the partial rows alone: no reduction coefficients, so no "+ 2*C" as in v2v_bn_backward) */
 int v2v_channel_sum(const void* x, float* out, int32_t accumulate, float* workspace,
                     int64_t P, int32_t C, int32_t c_stride, int32_t dtype, void* stream);
 /* Backward of a conv epilogue activation without norm: g = dY * act'(y) * out_scale.  dy / y are NHWC
