@@ -558,6 +558,26 @@ int v2v_warp_blend_roll_batch(float* img_raw, const float* flow, const float* we
                               const float* gx, const float* gy, float* window, int32_t slots,
                               int32_t N, int32_t C, int32_t H, int32_t W, int32_t align_corners, void* stream);
 
+/* Stream slots: v2v_warp_blend_roll_batch with one mode word per sample, mode[N] in device memory, read when the launch runs
+ * (a frame plan refreshes it per replay).  The kernel branches on the word; nothing is multiplied by a mask.
+ *   0  steady: sample n equals bit for bit v2v_warp_blend_roll_batch (with every mode 0 so do all outputs and the window);
+ *   1  raw-only first frame: flow and weight are not read, nothing is gathered, img_warp is not written, final = raw; the
+ *      foreground blend and the roll as in mode 0 -- bit for bit the one-sample call with flow = weight = NULL;
+ *   2  idle (and any other value): img_final = 0; img_raw, img_warp and the window are neither read nor written, so NaN in
+ *      the sample's inputs reaches nothing.
+ * window may be NULL: nothing is rolled (v2v_window_roll_slots does it); otherwise the overlap rule of v2v_warp_blend_roll_batch
+ * holds.  V2V_EINVAL for mode == NULL. */
+int v2v_warp_blend_slots(float* img_raw, const float* flow, const float* weight, const float* prev,
+                         const float* fg, const float* mask, float* img_final, float* img_warp,
+                         const float* gx, const float* gy, float* window, int32_t slots, const int32_t* mode,
+                         int32_t N, int32_t C, int32_t H, int32_t W, int32_t align_corners, void* stream);
+
+/* window [N][slots][C][H][W] <- frame [N][C][H][W], per sample under mode[N] (device memory): modes 0 and 1 roll (slot k <- slot
+ * k + 1, last slot <- frame), mode 2 (and any other value) leaves the sample's window untouched and does not read its frame.
+ * The thread that stores an element moves that element's slots.  V2V_EINVAL for mode == NULL or a frame inside the window. */
+int v2v_window_roll_slots(float* window, const float* frame, const int32_t* mode, int32_t N, int32_t slots,
+                          int32_t C, int32_t H, int32_t W, void* stream);
+
 /* Head of an inference frame whose label stems all read the 1-byte codes, in ONE launch:
  *   codes[T][H][W]   label | edge << 7, 127 = no label plane: bit for bit v2v_label_codes (in_u8 as there);
  *   mask[H][W]       (optional) foreground mask of frame T - 1: bit for bit what v2v_encode_labels* writes into `mask`;

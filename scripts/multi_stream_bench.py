@@ -9,6 +9,12 @@ rounds of (ms per replay) is reported, with min and max.  aggregate frames/s = B
 
     python scripts/multi_stream_bench.py [--streams 1,2,4,8] [--rounds 7] [--replays 40] [--json profiles/multi_stream_bench.json]
     python scripts/multi_stream_bench.py --streams 4 --rounds 1 --trace     # a short run to put under a kernel tracer
+    python scripts/multi_stream_bench.py --streams 4 --slots 8 [--json profiles/stream_slots_bench.json]
+
+--slots K measures, per B > 1 and inside the same alternating rounds, four arms: the plain plan's graph replay
+(`plain`), the slot plan's graph replay with every stream steady (`slots_steady`), and whole `inference()` calls -- input staging,
+mode copy, replay, output clones -- on the plain plan (`plain_calls`) and on the slot plan under a rolling schedule that restarts
+one slot every K frames, slot after slot (`slots_rolling`; the restart's first-frame work is inside the timed region).
 """
 import argparse
 import json
@@ -29,6 +35,7 @@ def main():
     ap.add_argument("--precision", default="bf16")
     ap.add_argument("--ngf", type=int, default=128)
     ap.add_argument("--json", default="")
+    ap.add_argument("--slots", type=int, default=0, help="K > 0: also time the slot plan; rolling schedule restarts one slot every K frames")
     ap.add_argument("--trace", action="store_true", help="no per-op table, few replays: for a run under a kernel tracer")
     args = ap.parse_args()
     import torch
@@ -103,11 +110,72 @@ def main():
     print("%8s %14s %22s %10s" % ("streams", "ms / replay", "aggregate frames/s", "vs B=1"))
     for r in rows:
         print("%8d %14.3f %22.1f %10s" % (r["streams"], r["ms_per_replay"], r["aggregate_frames_per_s"], r["vs_single_stream"]))
+    if args.slots > 0:
+        out["slots"] = slots_arms(args, model, inputs, [B for B in Bs if B > 1], plans, time_plan, dev)
     print(json.dumps(out))
     if args.json:
         with open(args.json, "w") as f:
             json.dump(out, f, indent=1)
             f.write("\n")
+
+
+def slots_arms(args, model, inputs, Bs, plans, time_plan, dev):
+    """The four arms of --slots for every B in Bs; returns {B: {arm: dict(ms, ms_min, ms_max, samples)}}."""
+    import torch
+    K = args.slots
+    slot_plans = {}
+    for B in Bs:
+        model.fake_B_prev = None
+        for t in range(2):
+            fake, _ = model.inference(*inputs(B, t), active=list(range(B)))
+        assert model._active_plan.slots and bool(torch.isfinite(fake).all())
+        slot_plans[B] = model._active_plan
+        names = [n for n, _, _ in slot_plans[B].plan.profile()]
+        assert "warp_blend_slots" in names and "memcpy_d2d" not in names
+    torch.cuda.synchronize(dev)
+    first = {B: inputs(B, 0) for B in Bs}
+    steady = {B: inputs(B, 1)[0::2] for B in Bs}
+
+    def time_calls(B, rolling, n):
+        """ms per inference() call over n calls of a running sequence; rolling: restart slot (i // K) % B every K-th call."""
+        A0, F0, I0 = first[B]
+        A1, I1 = steady[B]
+        model.fake_B_prev = None
+        kw = dict(active=list(range(B))) if rolling else {}
+        model.inference(A0, F0, I0, **kw)
+        for _ in range(3):
+            model.inference(A1, None, I1, **kw)
+        assert model._active_plan is (slot_plans[B] if rolling else plans[B])
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(n):
+            if rolling and i % K == 0:
+                model.inference(A0, F0, I0, restart=[(i // K) % B])
+            else:
+                model.inference(A1, None, I1)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    arms = {"plain": lambda B: time_plan(plans[B], args.replays), "slots_steady": lambda B: time_plan(slot_plans[B], args.replays),
+            "plain_calls": lambda B: time_calls(B, False, args.replays), "slots_rolling": lambda B: time_calls(B, True, args.replays)}
+    samples = {B: {a: [] for a in arms} for B in Bs}
+    order = list(arms)
+    for r in range(args.rounds):
+        for B in Bs:
+            for a in (order if r % 2 == 0 else order[::-1]):
+                samples[B][a].append(arms[a](B))
+    res = {}
+    print("%8s %16s %12s %10s %10s" % ("streams", "arm", "ms (median)", "min", "max"))
+    for B in Bs:
+        res[str(B)] = {}
+        for a in order:
+            v = sorted(samples[B][a])
+            res[str(B)][a] = dict(ms=round(v[len(v) // 2], 4), ms_min=round(v[0], 4), ms_max=round(v[-1], 4),
+                                  samples=[round(x, 4) for x in samples[B][a]])
+            print("%8d %16s %12.3f %10.3f %10.3f" % (B, a, v[len(v) // 2], v[0], v[-1]))
+        res[str(B)]["restart_every"] = K
+    return res
 
 
 if __name__ == "__main__":

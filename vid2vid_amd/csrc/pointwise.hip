@@ -708,6 +708,98 @@ struct WarpOp : Op {
     const char* name() const override { return "warp_blend"; }
 };
 
+// Stream slots (v2v_warp_blend_slots): the batched rolling blend with one mode word per sample, loaded once per element and
+// BRANCHED on (never a multiplication by a mask: an idle sample's NaN must not reach its zero row).
+//   0 steady    the arithmetic and store order of warp_blend_kernel<true>, expression for expression
+//   1 raw only  first frame of a sequence without a first image: no flow / weight read, no gather, fin = raw; the foreground
+//               blend and the roll as in mode 0 (what the kernel above does with flow == nullptr)
+//   other       idle: img_final = 0, nothing else of the sample is read or written (img_raw, img_warp, flow, the window)
+// a.roll may be null (the window is then rolled by window_roll_slots_kernel); it always has the batch layout [N][slots][C][H][W].
+struct WarpSlotArgs { WarpArgs w; const int* mode; };
+
+__global__ __launch_bounds__(256) void warp_blend_slots_kernel(const WarpSlotArgs s) {
+    const WarpArgs& a = s.w;
+    const long long hw = (long long)a.H * a.W;
+    const long long total = (long long)a.N * hw;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        const long long n = e / hw, pix = e - n * hw;
+        const int md = s.mode[n];
+        if (md != 0 && md != 1) {
+            for (int c = 0; c < a.C; ++c) a.img_final[(n * a.C + c) * hw + pix] = 0.f;
+            continue;
+        }
+        const int y = (int)(pix / a.W), x = (int)(pix - (long long)y * a.W);
+        int x0 = 0, y0 = 0; float wx = 0.f, wy = 0.f;
+        const bool do_warp = a.flow != nullptr && md == 0;
+        float wgt = 1.f;
+        if (do_warp) {
+            const float fx = a.flow[(n * 2 + 0) * hw + pix], fy = a.flow[(n * 2 + 1) * hw + pix];
+            bilinear_setup(fx, fy, a.gx[x], a.gy[y], a.H, a.W, a.align_corners, x0, y0, wx, wy);
+            wgt = a.weight[n * hw + pix];
+        }
+        const float m = a.fg ? a.mask[n * hw + pix] : 0.f;
+        for (int c = 0; c < a.C; ++c) {
+            const long long o = (n * a.C + c) * hw + pix;
+            float raw = a.img_raw[o];
+            float fin = raw;
+            if (do_warp) {
+                const float wv = bilinear_fetch(a.prev + (n * a.C + c) * hw, a.H, a.W, x0, y0, wx, wy);
+                if (a.img_warp) a.img_warp[o] = wv;
+                fin = raw * wgt + wv * (1.f - wgt);
+            }
+            if (a.fg) {
+                const float f = a.fg[o];
+                fin = f * m + fin * (1.f - m);
+                raw = f * m + raw * (1.f - m);
+                a.img_raw[o] = raw;
+            }
+            a.img_final[o] = fin;
+            if (a.roll) {                               // sample n's window: [slots][C][H][W]
+                float* w = a.roll + (n * a.roll_slots * a.C + c) * hw + pix;
+                const long long slot = (long long)a.C * hw;
+                for (int k = 0; k + 1 < a.roll_slots; ++k) w[k * slot] = w[(k + 1) * slot];
+                w[(a.roll_slots - 1) * slot] = fin;
+            }
+        }
+    }
+}
+
+struct WarpSlotsOp : Op {
+    WarpSlotArgs a;
+    int launch(hipStream_t s) override {
+        hipLaunchKernelGGL(warp_blend_slots_kernel, dim3(grid_for((long long)a.w.N * a.w.H * a.w.W)), dim3(256), 0, s, a);
+        return check_launch();
+    }
+    const char* name() const override { return "warp_blend_slots"; }
+};
+
+// v2v_window_roll_slots: window [N][slots][frame] <- frame [N][frame] for every sample whose mode is 0 or 1 (slot k <- slot k + 1,
+// last slot <- frame); the samples of any other mode are not touched.  One thread per frame element moves that element's slots.
+struct WindowRollArgs { float* window; const float* frame; const int* mode; long long frame_elems; int N, slots; };
+
+__global__ __launch_bounds__(256) void window_roll_slots_kernel(const WindowRollArgs a) {
+    const long long total = (long long)a.N * a.frame_elems;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        const long long n = e / a.frame_elems, r = e - n * a.frame_elems;
+        const int md = a.mode[n];
+        if (md != 0 && md != 1) continue;
+        float* w = a.window + n * a.slots * a.frame_elems + r;
+        for (int k = 0; k + 1 < a.slots; ++k) w[k * a.frame_elems] = w[(k + 1) * a.frame_elems];
+        w[(a.slots - 1) * a.frame_elems] = a.frame[e];
+    }
+}
+
+struct WindowRollOp : Op {
+    WindowRollArgs a;
+    int launch(hipStream_t s) override {
+        hipLaunchKernelGGL(window_roll_slots_kernel, dim3(grid_for((long long)a.N * a.frame_elems)), dim3(256), 0, s, a);
+        return check_launch();
+    }
+    const char* name() const override { return "window_roll_slots"; }
+};
+
 struct ResampleArgs { const float* img; const float* flow; float* out; const float* gx; const float* gy; int N, C, H, W, align_corners; };
 
 __global__ __launch_bounds__(256) void resample_flow_kernel(const ResampleArgs a) {
@@ -1333,6 +1425,45 @@ extern "C" int v2v_warp_blend_roll_batch(float* img_raw, const float* flow, cons
     auto op = std::make_unique<WarpOp>();
     op->a = WarpArgs{img_raw, flow, weight, prev, fg, mask, img_final, img_warp, gx, gy, N, C, H, W, align_corners};
     op->a.roll = window; op->a.roll_slots = slots;
+    return submit(std::move(op), stream);
+}
+
+extern "C" int v2v_warp_blend_slots(float* img_raw, const float* flow, const float* weight, const float* prev,
+                                    const float* fg, const float* mask, float* img_final, float* img_warp,
+                                    const float* gx, const float* gy, float* window, int32_t slots, const int32_t* mode,
+                                    int32_t N, int32_t C, int32_t H, int32_t W, int32_t align_corners, void* stream) {
+    if (!mode) { set_error("warp_blend_slots: null mode"); return V2V_EINVAL; }
+    if (!img_raw || !img_final || (flow && (!weight || !prev || !gx || !gy)) || (fg && !mask) || (window && slots < 1) ||
+        N < 1 || C < 1 || H < 1 || W < 1) {
+        set_error("warp_blend_slots: bad argument"); return V2V_EINVAL;
+    }
+    if (window) {       // as v2v_warp_blend_roll_batch: no sample's gather source or frame buffer inside any rolled window
+        const float* wend = window + (long long)N * slots * C * H * W;
+        const long long frame = (long long)N * C * H * W;
+        auto overlaps = [&](const float* p) { return p && p + frame > window && p < wend; };
+        if (overlaps(prev) || overlaps(img_final) || overlaps(img_raw) || overlaps(fg)) {
+            set_error("warp_blend_slots: the rolled window must not overlap the gather source or the frame buffers"); return V2V_EINVAL;
+        }
+    }
+    auto op = std::make_unique<WarpSlotsOp>();
+    op->a.w = WarpArgs{img_raw, flow, weight, prev, fg, mask, img_final, img_warp, gx, gy, N, C, H, W, align_corners};
+    op->a.w.roll = window; op->a.w.roll_slots = window ? slots : 0;
+    op->a.mode = mode;
+    return submit(std::move(op), stream);
+}
+
+extern "C" int v2v_window_roll_slots(float* window, const float* frame, const int32_t* mode, int32_t N, int32_t slots,
+                                     int32_t C, int32_t H, int32_t W, void* stream) {
+    if (!mode) { set_error("window_roll_slots: null mode"); return V2V_EINVAL; }
+    if (!window || !frame || N < 1 || slots < 1 || C < 1 || H < 1 || W < 1) {
+        set_error("window_roll_slots: bad argument"); return V2V_EINVAL;
+    }
+    const long long elems = (long long)C * H * W;
+    if (frame + N * elems > window && frame < window + (long long)N * slots * elems) {
+        set_error("window_roll_slots: the frame must not overlap the window"); return V2V_EINVAL;
+    }
+    auto op = std::make_unique<WindowRollOp>();
+    op->a = WindowRollArgs{window, frame, mode, elems, N, slots};
     return submit(std::move(op), stream);
 }
 

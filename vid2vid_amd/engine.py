@@ -2048,10 +2048,12 @@ class Engine:
         self.label("avgpool3s2_planar")
         return out
 
-    def warp_blend(self, img_raw, flow, weight, prev, fg, mask, want_warp=False, roll=None):
+    def warp_blend(self, img_raw, flow, weight, prev, fg, mask, want_warp=False, roll=None, slot_mode=None):
         """roll: the fp32 window (slots, C, H, W) of the last generated frames, oldest first -- the launch rolls it itself
         (v2v_warp_blend_roll; inference frame plans); (N, slots, C, H, W) for the N streams of a multi-stream plan
-        (v2v_warp_blend_roll_batch).  `prev` must then be a buffer outside the window."""
+        (v2v_warp_blend_roll_batch).  `prev` must then be a buffer outside the window.
+        slot_mode: int32 (N,) device tensor of per-stream modes (0 steady, 1 raw-only first frame, 2 idle), read by the launch
+        when it runs (v2v_warp_blend_slots; slot plans); roll is then (N, slots, C, H, W) or None."""
         N, Cc, H, W = img_raw.shape
         if self._training() and any(t is not None and t.requires_grad for t in (img_raw, flow, weight, prev, fg)):
             from . import autograd as AG
@@ -2062,6 +2064,19 @@ class Engine:
         warp = self.empty_f32(N, Cc, H, W) if (want_warp and flow is not None) else None
         for t in (gx, gy):
             self._keep(t)
+        if slot_mode is not None:
+            if slot_mode.dtype != torch.int32 or tuple(slot_mode.shape) != (N,) or not slot_mode.is_contiguous():
+                raise ValueError("warp_blend: slot_mode is int32 (N,)")
+            if roll is not None and (roll.dim() != 5 or tuple(roll.shape[2:]) != (Cc, H, W) or roll.shape[0] != N
+                                     or roll.dtype != torch.float32 or not roll.is_contiguous()):
+                raise ValueError("warp_blend: the rolled windows are fp32 (N, slots, C, H, W)")
+            self._keep(slot_mode)
+            check(lib.v2v_warp_blend_slots(_ptr(img_raw), _ptr(flow), _ptr(weight), _ptr(prev), _ptr(fg), _ptr(mask),
+                                           _ptr(final), _ptr(warp), _ptr(gx), _ptr(gy), _ptr(roll),
+                                           0 if roll is None else roll.shape[1], _ptr(slot_mode), N, Cc, H, W,
+                                           int(self.align_corners), _stream()), "warp_blend_slots")
+            self.label("warp_blend")
+            return final, warp
         if roll is not None and roll.dim() == 5:
             if tuple(roll.shape[2:]) != (Cc, H, W) or roll.shape[0] != N or roll.dtype != torch.float32 or not roll.is_contiguous():
                 raise ValueError("warp_blend: the rolled windows are fp32 (N, slots, C, H, W)")
@@ -2083,6 +2098,19 @@ class Engine:
                                  int(self.align_corners), _stream()), "warp_blend")
         self.label("warp_blend")
         return final, warp
+
+    def window_roll(self, window, frame, slot_mode):
+        """window (N, slots, C, H, W) <- frame (N, C, H, W) for the streams whose slot_mode is 0 or 1; an idle stream's window
+        is not touched (v2v_window_roll_slots: one launch instead of N * slots device copies)."""
+        N, slots, Cc, H, W = window.shape
+        if (tuple(frame.shape) != (N, Cc, H, W) or tuple(slot_mode.shape) != (N,) or slot_mode.dtype != torch.int32
+                or window.dtype != torch.float32 or frame.dtype != torch.float32
+                or not (window.is_contiguous() and frame.is_contiguous() and slot_mode.is_contiguous())):
+            raise ValueError("window_roll: fp32 window (N, slots, C, H, W), fp32 frame (N, C, H, W), int32 slot_mode (N,)")
+        self._keep(slot_mode)
+        check(lib.v2v_window_roll_slots(_ptr(window), _ptr(frame), _ptr(slot_mode), N, slots, Cc, H, W, _stream()),
+              "window_roll_slots")
+        self.label("window_roll")
 
     def resample_flow(self, img, flow):
         N, Cc, H, W = img.shape

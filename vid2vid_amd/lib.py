@@ -167,6 +167,8 @@ PROTOTYPES = {
     "v2v_warp_blend": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "v2v_warp_blend_roll": (C.c_int, [_P] * 11 + [_I] * 5 + [_P]),
     "v2v_warp_blend_roll_batch": (C.c_int, [_P] * 11 + [_I] * 6 + [_P]),
+    "v2v_warp_blend_slots": (C.c_int, [_P] * 11 + [_I] + [_P] + [_I] * 5 + [_P]),
+    "v2v_window_roll_slots": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "v2v_frame_prologue": (C.c_int, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P]),
     "v2v_frame_prologue_batch": (C.c_int, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P]),
     "v2v_resample_flow": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),

@@ -55,12 +55,18 @@ class _FramePlan:
     """Buffers + launch sequence generating one frame at every spatial scale, for B independent sequences (streams) per
     replay.  B == 1: the buffers have no stream dimension, exactly the single-sequence plan.  B > 1: every static
     buffer and output gets a leading B, and every norm group is lowered with per-sample statistics (Engine.per_stream), so
-    stream b computes what a batch-1 plan computes on sequence b alone."""
+    stream b computes what a batch-1 plan computes on sequence b alone.
+    slots (B > 1): the plan owns `slot_mode`, int32 (B,), refreshed per call -- 0 steady, 1 raw-only first frame,
+    2 idle -- and its tail launches (v2v_warp_blend_slots, v2v_window_roll_slots) branch on it per stream; everything in front
+    of the tail runs for all B streams whatever their mode."""
 
-    def __init__(self, model, H, W, in_ch, has_inst, use_raw_only, use_graph=True, u8=False, B=1):
+    def __init__(self, model, H, W, in_ch, has_inst, use_raw_only, use_graph=True, u8=False, B=1, slots=False):
         opt, eng = model.opt, model.engine
         self.model, self.eng = model, eng
         self.H, self.W, self.use_raw_only, self.B = H, W, use_raw_only, B
+        self.slots = bool(slots)
+        if self.slots and (B < 2 or use_raw_only):
+            raise ValueError("a slot plan has B > 1 streams and decides raw-only frames per stream (slot_mode 1)")
         lead = (B,) if B > 1 else ()
         tG, S = opt.n_frames_G, model.n_scales
         self.label_mode = opt.label_nc != 0
@@ -78,6 +84,14 @@ class _FramePlan:
         # fake_B_prev[si]: (tG-1, 3, h, w) per scale, si = 0 finest  (reference :228, :248-250); (B, tG-1, 3, h, w) at B > 1
         self.prev = [torch.zeros(*lead, tG - 1, opt.output_nc, H >> si, W >> si, dtype=torch.float32, device=dev)
                      for si in range(S)]
+        self.slot_mode = self.slot_mode_host = self._slot_mode_copied = None
+        if self.slots:
+            self.slot_mode = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.slot_mode_host = torch.zeros(B, dtype=torch.int32)
+            if dev.type == "cuda":
+                self.slot_mode_host = self.slot_mode_host.pin_memory()
+            # does the finest generator end in the blend launch (which writes an idle stream's row of zeros)?
+            self.blend_launch = getattr(model, "netG" + str(S - 1)).blends_in_tail()
         self.out = {}
         # independent towers / branches on parallel plan lanes (parallel hipGraph paths); opt.lanes or V2V_LANES
         self.lanes = bool(int(getattr(opt, "lanes", os.environ.get("V2V_LANES", "1")))) and use_graph
@@ -255,7 +269,7 @@ class _FramePlan:
             prev_nchw = self.prev[si].view(B, -1, H >> si, W >> si)
             fake_B, flow, weight, raw, feat, flow_feat, fg_feat = netG.emit(
                 eng, x, eng.pack(prev_nchw), prev_nchw, mask, feat, flow_feat, fg_feat, self.use_raw_only,
-                tag="G%d" % s)
+                tag="G%d" % s, slot_mode=self.slot_mode)
             # fake_B_prev[si] = cat(prev[1:], fake_B)   (:228)
             self._roll(self.prev[si], fake_B)
             self.out["flow%d" % si], self.out["weight%d" % si], self.out["raw%d" % si] = flow, weight, raw
@@ -292,7 +306,8 @@ class _FramePlan:
             self.out["real_A_last"] = self._real_A_last()
         roll = prev if netG.rolls_in_tail(self.use_raw_only) else None
         fake_B, flow, weight, raw, _, _, _ = netG.emit(eng, x0, prev_act, last, mask0, None, None, None, self.use_raw_only,
-                                                       tag="G0", roll=roll, side=real_A_last)
+                                                       tag="G0", roll=roll, side=real_A_last,
+                                                       slot_mode=self.slot_mode)
         if roll is None:
             self._roll(prev, fake_B)
         self.out["flow0"], self.out["weight0"], self.out["raw0"] = flow, weight, raw
@@ -300,7 +315,9 @@ class _FramePlan:
         self.conv_log = list(eng.conv_log)
 
     def _roll(self, prev, fake_B):
-        if self.B > 1:                   # (B, tG-1, 3, h, w) <- (B, 3, h, w): every stream rolls its own window
+        if self.slots:                   # one launch under slot_mode: an idle stream's window is not touched
+            self.eng.window_roll(prev, fake_B, self.slot_mode)
+        elif self.B > 1:                 # (B, tG-1, 3, h, w) <- (B, 3, h, w): every stream rolls its own window
             for b in range(self.B):
                 self._roll_one(prev[b], fake_B[b])
         else:
@@ -316,6 +333,17 @@ class _FramePlan:
     def _mask_from_pooled(self, x, per, tG):
         # compute_mask on a pooled (fractional) one-hot pyramid level: clamp(sum of fg channels)
         return self.eng.fg_mask(x, (tG - 1) * per, self.model.opt.fg_labels)
+
+    def set_slot_modes(self, modes):
+        """Refresh slot_mode for the next replay: one 4*B-byte asynchronous copy from pinned host memory, like the label buffers.
+        (The host buffer is rewritten only after the previous copy out of it has completed.)"""
+        if self._slot_mode_copied is not None:
+            self._slot_mode_copied.synchronize()
+        self.slot_mode_host.copy_(torch.as_tensor(modes, dtype=torch.int32))
+        self.slot_mode.copy_(self.slot_mode_host, non_blocking=True)
+        if self.slot_mode.device.type == "cuda":
+            self._slot_mode_copied = torch.cuda.Event()
+            self._slot_mode_copied.record()
 
     def run(self):
         if self.eng.record_only:
@@ -383,22 +411,54 @@ class Vid2VidModelG(BaseModel):
         self.bind_precision()
 
     # ------------------------------------------------------------------ inference
-    def _frame_plan(self, H, W, in_ch, has_inst, use_raw_only, u8=False, B=1):
-        key = (H, W, in_ch, has_inst, use_raw_only, self.precision, u8, B)
+    def _frame_plan(self, H, W, in_ch, has_inst, use_raw_only, u8=False, B=1, slots=False):
+        key = (H, W, in_ch, has_inst, use_raw_only, self.precision, u8, B) + (("slots",) if slots else ())
         fp = self._plans.get(key)
         if fp is None:
             self.engine.refresh_weights()
             fp = _FramePlan(self, H, W, in_ch, has_inst, use_raw_only,
-                            use_graph=getattr(self.opt, "use_graph", True), u8=u8, B=B)
+                            use_graph=getattr(self.opt, "use_graph", True), u8=u8, B=B, slots=slots)
             self._plans[key] = fp
         return fp
 
-    def inference(self, input_A, input_B, inst_A):
+    @staticmethod
+    def _slot_set(arg, B, name):
+        """restart= / active= as a list of B bools: a bool mask of shape (B,) or an iterable of stream indices."""
+        if isinstance(arg, torch.Tensor):
+            arg = arg.detach().cpu()
+            is_mask = arg.dtype == torch.bool
+            items = arg.reshape(-1).tolist() if arg.dim() <= 1 else None
+        else:
+            if hasattr(arg, "tolist"):          # numpy arrays
+                arg = arg.tolist()
+            items = list(arg) if not isinstance(arg, (bool, int)) else None
+            is_mask = items is not None and len(items) > 0 and all(isinstance(v, bool) for v in items)
+        if items is None:
+            raise ValueError("inference: %s is a bool mask of shape (%d,) or an iterable of stream indices" % (name, B))
+        if is_mask:
+            if len(items) != B:
+                raise ValueError("inference: %s mask has %d entries for %d stream(s)" % (name, len(items), B))
+            return [bool(v) for v in items]
+        flags = [False] * B
+        for v in items:
+            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) < B:
+                raise ValueError("inference: %s names stream %r, the call has streams 0..%d" % (name, v, B - 1))
+            flags[int(v)] = True
+        return flags
+
+    def inference(self, input_A, input_B, inst_A, restart=None, active=None):
         """(fake_B (B,3,H,W), real_A_last) for the newest of the tG label frames of each of the B sequences in input_A
         (B,t,c,H,W); inst_A / input_B carry the same leading B.  B == 1: real_A_last is (C,H,W) and model.fake_B_prev a list
         per scale of (tG-1,3,h,w), as in the reference.  B > 1 (multi-stream): real_A_last is (B,C,H,W),
         fake_B_prev a list per scale of (B,tG-1,3,h,w), and stream b gets what a batch-1 model gets on sequence b alone.
-        Changing B inside a sequence (fake_B_prev not None) is a ValueError; fake_B_prev = None restarts all streams."""
+        Changing B inside a sequence (fake_B_prev not None) is a ValueError; fake_B_prev = None restarts all streams.
+        Stream slots, both a bool mask (B,) or an iterable of stream indices:
+        active: the streams that generate a frame in this call (default: all).  An idle stream's rows of the inputs are not
+        read, its windows fake_B_prev[si][b] stay bit for bit as they are, its row of fake_B is zero; when it is active again
+        it continues where it paused.
+        restart: the streams that begin a new sequence with this call: their windows are re-seeded by generate_first_frame on
+        their rows alone (input_B rows of the other streams are ignored).  restart implies active; a stream that is restarted
+        and idle, an index outside [0, B) or a mask of another length is a ValueError."""
         opt = self.opt
         tG = opt.n_frames_G
         with torch.no_grad():
@@ -408,14 +468,39 @@ class Vid2VidModelG(BaseModel):
             for name, t in (("inst_A", inst_A if opt.use_instance else None), ("input_B", input_B)):
                 if t is not None and t.shape[0] != B:
                     raise ValueError("inference: input_A holds %d sequence(s), %s %d" % (B, name, t.shape[0]))
+            slot_call = restart is not None or active is not None
+            if slot_call:
+                act = [True] * B if active is None else self._slot_set(active, B, "active")
+                rst = [False] * B if restart is None else self._slot_set(restart, B, "restart")
+                both = [b for b in range(B) if rst[b] and not act[b]]
+                if both:
+                    raise ValueError("inference: stream(s) %s are restarted and idle in the same call" % both)
             self._check_device_status()
             self.is_first_frame = not hasattr(self, "fake_B_prev") or self.fake_B_prev is None
             if not self.is_first_frame and self._active_plan is not None and self._active_plan.B != B:
                 raise ValueError("inference: %d sequence(s) given while %d are running; assign fake_B_prev = None to restart"
                                  % (B, self._active_plan.B))
-            use_raw_only = bool(opt.no_first_img and self.is_first_frame)
             has_inst = bool(opt.use_instance and inst_A is not None and opt.label_nc != 0)
+            if slot_call and B == 1:
+                # one stream needs no slot plan: idle is no call at all, a restart is fake_B_prev = None
+                if not act[0]:
+                    last_C = in_ch if opt.label_nc == 0 else opt.label_nc + int(has_inst)
+                    return (torch.zeros(1, opt.output_nc, H, W, dtype=torch.float32, device=self.device),
+                            torch.zeros(last_C, H, W, dtype=torch.float32, device=self.device))
+                if rst[0]:
+                    self.fake_B_prev = None
+                    self.is_first_frame = True
+                slot_call = False
+            if self.is_first_frame:
+                self._slots_on = False
+            if slot_call:
+                self._slots_on = True            # sticky until fake_B_prev = None
             u8 = bool(opt.label_nc != 0 and input_A.dtype == torch.uint8)
+            if self._slots_on:
+                if not slot_call:
+                    act, rst = [True] * B, [False] * B
+                return self._inference_slots(input_A, input_B, inst_A, act, rst, has_inst, u8)
+            use_raw_only = bool(opt.no_first_img and self.is_first_frame)
             fp = self._frame_plan(H, W, in_ch, has_inst, use_raw_only, u8, B)
             dev = self.device
             # ---- stage inputs (H2D or D2D) into the plan's static buffers; pinned host tensors copy asynchronously ----
@@ -438,6 +523,50 @@ class Vid2VidModelG(BaseModel):
             # fresh tensors per frame, as the reference returns them (the plan's output buffers are overwritten by the
             # next replay; a caller collecting a clip must not see every entry alias the last frame)
             return fp.out["fake_B"].clone(), fp.out["real_A_last"].clone()
+
+    def _inference_slots(self, input_A, input_B, inst_A, act, rst, has_inst, u8):
+        """One replay of the slot plan (B > 1).  act / rst: B bools.  On the first frame of the model
+        (fake_B_prev = None) every active stream starts a sequence and the windows of the idle ones are zero."""
+        opt, dev = self.opt, self.device
+        tG = opt.n_frames_G
+        B, _, in_ch, H, W = input_A.shape
+        fp = self._frame_plan(H, W, in_ch, has_inst, False, u8, B, slots=True)
+        if self.is_first_frame:
+            rst = list(act)
+        # ---- stage the rows of the active streams; an idle stream's rows are not read (the buffers keep its last valid rows) ----
+        rows = [b for b in range(B) if act[b]]
+        for sel in ([slice(None)] if len(rows) == B else rows):
+            if fp.label_mode:
+                fp.labels[sel].copy_(input_A[sel, :tG, 0].to(dev, fp.labels.dtype, non_blocking=True))
+                if has_inst:
+                    fp.inst[sel].copy_(inst_A[sel, :tG, 0].to(dev, fp.inst.dtype, non_blocking=True))
+            else:
+                fp.raw_in[sel].copy_(input_A[sel, :tG].reshape(fp.raw_in[sel].shape).to(dev, torch.float32, non_blocking=True))
+        # ---- windows ----
+        if self.is_first_frame:
+            for si in range(self.n_scales):
+                fp.prev[si].zero_()
+        elif self._active_plan is not fp:
+            for si in range(self.n_scales):                                      # plain plan -> slot plan
+                fp.prev[si].copy_(self._active_plan.prev[si])
+        new = [b for b in range(B) if rst[b]]
+        if new:
+            first = self.generate_first_frame(input_A[new], None if input_B is None else input_B[new],
+                                              None if inst_A is None else inst_A[new])
+            for si in range(self.n_scales):
+                if len(new) == 1:
+                    fp.prev[si][new[0]].copy_(first[si])
+                else:
+                    for k, b in enumerate(new):
+                        fp.prev[si][b].copy_(first[si][k])
+        fp.set_slot_modes([2 if not act[b] else (1 if (rst[b] and opt.no_first_img) else 0) for b in range(B)])
+        self._active_plan = fp
+        self.fake_B_prev = fp.prev
+        fp.run()
+        fake = fp.out["fake_B"].clone()
+        if not fp.blend_launch and len(rows) != B:        # no blend launch in this generator: nothing wrote the idle rows' zeros
+            fake[[b for b in range(B) if not act[b]]] = 0
+        return fake, fp.out["real_A_last"].clone()
 
     def _check_device_status(self):
         """Kernels cannot return errors; the library's host-visible status word says whether a fused-norm spin barrier of
@@ -660,3 +789,4 @@ class Vid2VidModelG(BaseModel):
             self.save_network(getattr(self, "netG" + str(s)), "G" + str(s), label, self.gpu_ids)
 
     _active_plan = None
+    _slots_on = False

@@ -245,9 +245,15 @@ class BaseNetwork(nn.Module):
         eng = module_engine(self, image.device)
         return eng.resample_flow(image.contiguous().float(), flow.contiguous().float())
 
-    def _tail(self, eng, img_raw, flow, weight, img_prev_nchw, img_fg, mask, use_raw_only, roll=None):
+    def blends_in_tail(self, use_raw_only=False):
+        """Does emit end in the warp / blend launch?  (Without one the generated frame IS the image head's output.)"""
+        return not (use_raw_only or self.no_flow) or self.use_fg_model
+
+    def _tail(self, eng, img_raw, flow, weight, img_prev_nchw, img_fg, mask, use_raw_only, roll=None, slot_mode=None):
         """models/networks.py:215-230 / :309-323 as one fused launch.  roll: the frame plan's window of generated frames, rolled
-        by that launch (Engine.warp_blend); img_prev_nchw is then a buffer of its own."""
+        by that launch (Engine.warp_blend); img_prev_nchw is then a buffer of its own.
+        slot_mode: per-stream modes of a slot plan -- the blend launch decides per stream between the steady
+        frame, the raw-only first frame and an idle row of zeros; use_raw_only is then False."""
         do_warp = not (use_raw_only or self.no_flow)
         if not do_warp and img_fg is None:
             if roll is not None:
@@ -260,7 +266,7 @@ class BaseNetwork(nn.Module):
         if mask is not None:
             mask = mask.contiguous().float()
         res, _ = eng.warp_blend(img_raw, flow if do_warp else None, weight if do_warp else None, prev3,
-                                img_fg, mask if img_fg is not None else None, roll=roll)
+                                img_fg, mask if img_fg is not None else None, roll=roll, slot_mode=slot_mode)
         if isinstance(res, tuple):          # training graph: (img_final, blended img_raw), inputs untouched
             return res
         return res, img_raw                 # inference: img_raw was blended in place
@@ -343,9 +349,9 @@ class CompositeGenerator(BaseNetwork):
         return convs
 
     def emit(self, eng, x, prev, img_prev_nchw, mask, img_feat_coarse, flow_feat_coarse, img_fg_feat_coarse,
-             use_raw_only, tag="G0", roll=None, side=None):
+             use_raw_only, tag="G0", roll=None, side=None, slot_mode=None):
         """x: Act labels (NHWC), prev: Act previous frames (NHWC), img_prev_nchw: fp32 planar.
-        roll: see _tail (rolls_in_tail says whether this configuration has the launch that does it).
+        roll, slot_mode: see _tail (rolls_in_tail says whether this configuration has the launch that does it).
         side: a callable that emits launches nothing here depends on (the frame plan's real_A_last): called behind the
         foreground tower, on its lane -- the one furthest off the frame's critical path -- or in front of the tail without one.
         The label tower, the image tower and the foreground tower are independent until they are summed / blended, and
@@ -449,7 +455,8 @@ class CompositeGenerator(BaseNetwork):
             eng.join(1)
             if self.use_fg_model:
                 eng.join(2)
-        img_final, img_raw = self._tail(eng, img_raw, flow, weight, img_prev_nchw, img_fg, mask, use_raw_only, roll=roll)
+        img_final, img_raw = self._tail(eng, img_raw, flow, weight, img_prev_nchw, img_fg, mask, use_raw_only, roll=roll,
+                                        slot_mode=slot_mode)
         return img_final, flow, weight, img_raw, img_feat, flow_feat, img_fg_feat
 
     def rolls_in_tail(self, use_raw_only):
@@ -526,7 +533,7 @@ class CompositeLocalGenerator(BaseNetwork):
         return convs
 
     def emit(self, eng, x, prev, img_prev_nchw, mask, img_feat_coarse, flow_feat_coarse, img_fg_feat_coarse,
-             use_raw_only, tag="G1"):
+             use_raw_only, tag="G1", slot_mode=None):
         """Same lane structure as CompositeGenerator.emit: label stem | image stem | foreground branch in parallel, then
         image branch | flow branch (models/networks.py:296-325)."""
         lanes = eng.lanes_enabled
@@ -574,7 +581,7 @@ class CompositeLocalGenerator(BaseNetwork):
             eng.join(1)
             if self.use_fg_model:
                 eng.join(2)
-        img_final, img_raw = self._tail(eng, img_raw, flow, weight, img_prev_nchw, img_fg, mask, use_raw_only)
+        img_final, img_raw = self._tail(eng, img_raw, flow, weight, img_prev_nchw, img_fg, mask, use_raw_only, slot_mode=slot_mode)
         return img_final, flow, weight, img_raw, img_feat, flow_feat, img_fg_feat
 
     def forward(self, input, img_prev, mask, img_feat_coarse, flow_feat_coarse, img_fg_feat_coarse, use_raw_only):
