@@ -596,6 +596,41 @@ int v2v_frame_prologue_batch(const void* labels, const void* inst, int32_t in_u8
                              int32_t label_nc, const float* window, int32_t win_C, void* packed, int32_t c_stride,
                              float* last, int32_t last_C, int32_t dtype, void* stream);
 
+/* Stream pool (a K-row plan serving K of S slots): row_slot[K], int32 in device memory, read when the launch runs (a frame plan
+ * refreshes it per replay), names the slot of the pool that dense row k works on.  The word is loaded once per row (the row is a
+ * grid dimension) and branched on.  A row whose word is outside [0, S) does nothing: no window is read or written and the row's
+ * dense outputs are left unwritten.  The words of one launch must be distinct (two rows on one slot race).
+ *
+ * v2v_frame_prologue_batch over K dense rows: labels / inst / codes [K][T][H][W], mask [K][H][W], packed [K][H][W][c_stride], last
+ * [K][last_C][H][W]; window is the pool [S][win_C][H][W] and row k packs and copies from slot row_slot[k].  Row k equals bit for
+ * bit the one-sample call on that slot's window; with row_slot the identity and K = S so does every output of
+ * v2v_frame_prologue_batch.  V2V_EINVAL for row_slot == NULL or window == NULL. */
+int v2v_frame_prologue_pool(const void* labels, const void* inst, int32_t in_u8, uint8_t* codes, float* mask,
+                            const int32_t* fg_labels_dev, int32_t n_fg, int32_t K, int32_t T, int32_t H, int32_t W,
+                            int32_t label_nc, const float* window, int32_t S, const int32_t* row_slot, int32_t win_C, void* packed,
+                            int32_t c_stride, float* last, int32_t last_C, int32_t dtype, void* stream);
+
+/* v2v_warp_blend_slots with every per-sample tensor dense [K] and the rolled window the pool [S][slots][C][H][W]: row k rolls
+ * slot row_slot[k].  mode[K] (device memory) is 0 (steady) or 1 (raw-only first frame) as there; a row of any other mode does
+ * nothing, like a row whose slot is out of range.  Row k equals bit for bit the one-sample v2v_warp_blend_roll on its tensors and
+ * its slot's window (mode 1: with flow = weight = NULL); slots not named keep their window bit for bit; with row_slot the identity
+ * and K = S every output and the window equal v2v_warp_blend_slots.  No frame buffer of any row may overlap any slot of the pool
+ * (checked).  V2V_EINVAL for mode == NULL, row_slot == NULL or window == NULL. */
+int v2v_warp_blend_pool(float* img_raw, const float* flow, const float* weight, const float* prev,
+                        const float* fg, const float* mask, float* img_final, float* img_warp,
+                        const float* gx, const float* gy, float* window, int32_t slots, const int32_t* mode,
+                        const int32_t* row_slot, int32_t K, int32_t S, int32_t C, int32_t H, int32_t W, int32_t align_corners,
+                        void* stream);
+
+/* dense [K][slots][C][H][W] <- pool [row_slot[k]][slots][C][H][W] (gather) and the inverse (scatter), fp32, 16-byte vectors where
+ * a window is whole vectors and both bases are aligned.  Gather then scatter is the identity on the named slots; slots not named
+ * are not touched.  They serve the frame plans that do not end in the rolling blend.  V2V_EINVAL for a null pointer or where
+ * dense and pool overlap. */
+int v2v_window_gather_pool(float* dense, const float* pool, const int32_t* row_slot, int32_t K, int32_t S, int32_t slots,
+                           int32_t C, int32_t H, int32_t W, void* stream);
+int v2v_window_scatter_pool(float* pool, const float* dense, const int32_t* row_slot, int32_t K, int32_t S, int32_t slots,
+                            int32_t C, int32_t H, int32_t W, void* stream);
+
 /* Backward of v2v_warp_blend.  raw = the PRE-blend img_raw; d_rawout = gradient w.r.t. the blended
  * img_raw output (NULL if unused); d_prev (optional) must be pre-zeroed, it is accumulated atomically
  * like ATen's grid_sampler backward.  Gradient through the border clip follows ATen

@@ -15,6 +15,13 @@ rounds of (ms per replay) is reported, with min and max.  aggregate frames/s = B
 (`plain`), the slot plan's graph replay with every stream steady (`slots_steady`), and whole `inference()` calls -- input staging,
 mode copy, replay, output clones -- on the plain plan (`plain_calls`) and on the slot plan under a rolling schedule that restarts
 one slot every K frames, slot after slot (`slots_rolling`; the restart's first-frame work is inside the timed region).
+
+    python scripts/multi_stream_bench.py --streams 1 --pool 4 [--json profiles/stream_pool_bench.json]
+
+--pool S times whole `inference()` calls of a running server with S slots of which K = 1..S are active (slots
+0..K-1; the others idle), inside the same alternating rounds: `pool` (opt.compact_streams: the K-row pool plan), `slots_idle`
+(the S-row slot plan with the same S - K slots idle) and `dense` (a plain call with K streams: the K-row plan without a pool).
+The pool plans are built ahead with prepare_streams.
 """
 import argparse
 import json
@@ -36,6 +43,7 @@ def main():
     ap.add_argument("--ngf", type=int, default=128)
     ap.add_argument("--json", default="")
     ap.add_argument("--slots", type=int, default=0, help="K > 0: also time the slot plan; rolling schedule restarts one slot every K frames")
+    ap.add_argument("--pool", type=int, default=0, help="S > 1: time inference() calls with K = 1..S of S slots active, compact vs slot plan vs dense")
     ap.add_argument("--trace", action="store_true", help="no per-op table, few replays: for a run under a kernel tracer")
     args = ap.parse_args()
     import torch
@@ -112,6 +120,8 @@ def main():
         print("%8d %14.3f %22.1f %10s" % (r["streams"], r["ms_per_replay"], r["aggregate_frames_per_s"], r["vs_single_stream"]))
     if args.slots > 0:
         out["slots"] = slots_arms(args, model, inputs, [B for B in Bs if B > 1], plans, time_plan, dev)
+    if args.pool > 1:
+        out["pool"] = pool_arms(args, model, args.pool, H, W, dev)
     print(json.dumps(out))
     if args.json:
         with open(args.json, "w") as f:
@@ -175,6 +185,69 @@ def slots_arms(args, model, inputs, Bs, plans, time_plan, dev):
                                   samples=[round(x, 4) for x in samples[B][a]])
             print("%8d %16s %12.3f %10.3f %10.3f" % (B, a, v[len(v) // 2], v[0], v[-1]))
         res[str(B)]["restart_every"] = K
+    return res
+
+
+def pool_arms(args, model, S, H, W, dev):
+    """The three arms of --pool for K = 1..S active of S slots; returns {K: {arm: dict(ms, ms_min, ms_max, samples)}}."""
+    import torch
+    from vid2vid_amd import synthetic
+    opt = model.opt
+    tG = opt.n_frames_G
+    seqs = [synthetic.label2city_sequence(tG + 2, H, W, seed=1234 + b, device=dev) for b in range(S)]
+
+    def inputs(B, t):
+        A = torch.stack([q[0][t:t + tG] for q in seqs[:B]]).view(B, tG, 1, H, W)
+        I = torch.stack([q[1][t:t + tG] for q in seqs[:B]]).view(B, tG, 1, H, W)
+        return A, (torch.cat([q[2][:, :tG - 1] for q in seqs[:B]]) if t == 0 else None), I
+
+    opt.compact_streams = True
+    model.prepare_streams(S, H, W, 1, True)
+    opt.compact_streams = False
+
+    def time_calls(arm, K, n):
+        B = K if arm == "dense" else S
+        kw = {} if arm == "dense" else dict(active=list(range(K)))
+        opt.compact_streams = arm == "pool"
+        try:
+            model.fake_B_prev = None
+            model.inference(*inputs(B, 0), **kw)
+            A1, _, I1 = inputs(B, 1)
+            for _ in range(3):
+                fake, _ = model.inference(A1, None, I1, **kw)
+            fp = model._active_plan
+            assert (fp.pool is not None) == (arm == "pool") and fp.B == (S if arm == "slots_idle" else K)
+            assert bool(torch.isfinite(fake).all()) and (arm == "dense" or K == S or not fake[K:].any())
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(n):
+                model.inference(A1, None, I1, **kw)
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_time(e1) / n
+        finally:
+            opt.compact_streams = False
+
+    order = ["pool", "slots_idle", "dense"]
+    Ks = list(range(1, S + 1))
+    for K in Ks:                                    # build every plan (tile search included) outside the timed rounds
+        for a in order:
+            time_calls(a, K, 2)
+    samples = {K: {a: [] for a in order} for K in Ks}
+    for r in range(args.rounds):
+        for K in (Ks if r % 2 == 0 else Ks[::-1]):
+            for a in (order if r % 2 == 0 else order[::-1]):
+                samples[K][a].append(time_calls(a, K, args.replays))
+    res = {}
+    print("%8s %12s %12s %10s %10s" % ("active", "arm", "ms (median)", "min", "max"))
+    for K in Ks:
+        res[str(K)] = {}
+        for a in order:
+            v = sorted(samples[K][a])
+            res[str(K)][a] = dict(ms=round(v[len(v) // 2], 4), ms_min=round(v[0], 4), ms_max=round(v[-1], 4),
+                                  samples=[round(x, 4) for x in samples[K][a]])
+            print("%8d %12s %12.3f %10.3f %10.3f" % (K, a, v[len(v) // 2], v[0], v[-1]))
+    res["slots"] = S
     return res
 
 

@@ -505,6 +505,85 @@ struct PrologueOp : Op {
     const char* name() const override { return "frame_prologue"; }
 };
 
+// Stream pool (v2v_frame_prologue_pool): the batched kernel above over K dense rows whose window is slot row_slot[row] of the pool
+// [S][win_C][H][W].  The slot word is loaded once per workgroup (blockIdx.y is the row: wave-uniform) and branched on; a row whose
+// word is outside [0, S) returns before it reads or writes anything.  Per element the expressions and the store order are those
+// of frame_prologue_kernel.
+struct ProloguePoolArgs { PrologueArgs p; const int* row_slot; int S; };
+
+template <typename T, typename LT, typename IT>
+__global__ __launch_bounds__(256) void frame_prologue_pool_kernel(const ProloguePoolArgs s) {
+    const PrologueArgs& a = s.p;
+    constexpr int VEC = ElemTraits<T>::VEC;
+    const long long nb = (long long)blockIdx.y;
+    const int slot = s.row_slot[nb];
+    if (slot < 0 || slot >= s.S) return;
+    const long long hw = (long long)a.H * a.W;
+    const long long ncode = hw * a.T;
+    const int vpr = a.c_stride / VEC;
+    const long long total = ncode + hw * vpr;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const LT* labels = reinterpret_cast<const LT*>(a.labels) + nb * ncode;
+    const IT* inst = a.inst ? reinterpret_cast<const IT*>(a.inst) + nb * ncode : nullptr;
+    unsigned char* codes = a.codes + nb * ncode;
+    float* mask = a.mask ? a.mask + nb * hw : nullptr;
+    const float* window = a.window + (long long)slot * a.win_C * hw;
+    float* last = a.last ? a.last + nb * a.last_C * hw : nullptr;
+    T* y = reinterpret_cast<T*>(a.packed) + nb * hw * a.c_stride;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        if (e < ncode) {
+            const long long t = e / hw, q = e - t * hw;
+            const int lab = (int)labels[e];
+            bool edge = false;
+            if (inst) {
+                const int py = (int)(q / a.W), px = (int)(q - (long long)py * a.W);
+                const IT* ip = inst + t * hw;
+                const IT ctr = ip[q];
+                if (px > 0)       edge |= ip[q - 1] != ctr;
+                if (px < a.W - 1) edge |= ip[q + 1] != ctr;
+                if (py > 0)       edge |= ip[q - a.W] != ctr;
+                if (py < a.H - 1) edge |= ip[q + a.W] != ctr;
+            }
+            codes[e] = (unsigned char)(((unsigned)lab < (unsigned)a.label_nc ? lab : 127) | (edge ? 128 : 0));
+            if (mask && t == a.T - 1) {
+                float m = 0.f;
+                for (int i = 0; i < a.n_fg; ++i) m += (a.fg[i] == lab) ? 1.f : 0.f;
+                mask[q] = fminf(fmaxf(m, 0.f), 1.f);
+            }
+        } else {
+            const long long v = e - ncode;
+            const long long pix = v % hw;
+            const int cv = (int)(v / hw);
+            float vals[VEC];
+#pragma unroll
+            for (int q = 0; q < VEC; ++q) {
+                const int c = cv * VEC + q;
+                vals[q] = c < a.win_C ? window[c * hw + pix] : 0.f;
+                if (last && c < a.win_C && c >= a.win_C - a.last_C) last[(c - (a.win_C - a.last_C)) * hw + pix] = vals[q];
+            }
+            store_vec(y, pix * a.c_stride + cv * VEC, vals);
+        }
+    }
+}
+
+struct ProloguePoolOp : Op {
+    ProloguePoolArgs a; int dtype; int in_u8;
+    int launch(hipStream_t s) override {
+        const int vec = dtype == V2V_BF16 ? 8 : 4;
+        const long long hw = (long long)a.p.H * a.p.W;
+        const dim3 g(grid_for(hw * a.p.T + hw * (a.p.c_stride / vec)), (unsigned)a.p.N), b(256);
+        if (in_u8) {
+            if (dtype == V2V_BF16) hipLaunchKernelGGL((frame_prologue_pool_kernel<bf16_t, unsigned char, int>), g, b, 0, s, a);
+            else                   hipLaunchKernelGGL((frame_prologue_pool_kernel<float, unsigned char, int>), g, b, 0, s, a);
+        } else {
+            if (dtype == V2V_BF16) hipLaunchKernelGGL((frame_prologue_pool_kernel<bf16_t, float, float>), g, b, 0, s, a);
+            else                   hipLaunchKernelGGL((frame_prologue_pool_kernel<float, float, float>), g, b, 0, s, a);
+        }
+        return check_launch();
+    }
+    const char* name() const override { return "frame_prologue_pool"; }
+};
+
 // ---------------------------------------------------------------------------------------
 // AvgPool2d(3, stride 2, padding 1, count_include_pad=False)
 // ---------------------------------------------------------------------------------------
@@ -798,6 +877,101 @@ struct WindowRollOp : Op {
         return check_launch();
     }
     const char* name() const override { return "window_roll_slots"; }
+};
+
+// Stream pool (v2v_warp_blend_pool): warp_blend_slots_kernel over K dense rows that roll slot row_slot[row] of the pool
+// [S][slots][C][H][W].  blockIdx.y is the row, so its two words (slot, mode) are loaded once per workgroup and are wave-uniform.
+// mode 0 and 1 as in warp_blend_slots_kernel, expression for expression; a row of any other mode, or whose slot is outside [0, S),
+// returns before it reads or writes anything.
+struct WarpPoolArgs { WarpArgs w; const int* mode; const int* row_slot; int S; };
+
+__global__ __launch_bounds__(256) void warp_blend_pool_kernel(const WarpPoolArgs s) {
+    const WarpArgs& a = s.w;
+    const long long n = (long long)blockIdx.y;
+    const int slot = s.row_slot[n], md = s.mode[n];
+    if (slot < 0 || slot >= s.S || (md != 0 && md != 1)) return;
+    const long long hw = (long long)a.H * a.W;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const bool do_warp = a.flow != nullptr && md == 0;
+    float* const win = a.roll + (long long)slot * a.roll_slots * a.C * hw;      // this row's window: [slots][C][H][W]
+    for (long long pix = (long long)blockIdx.x * blockDim.x + threadIdx.x; pix < hw; pix += stride) {
+        const int y = (int)(pix / a.W), x = (int)(pix - (long long)y * a.W);
+        int x0 = 0, y0 = 0; float wx = 0.f, wy = 0.f;
+        float wgt = 1.f;
+        if (do_warp) {
+            const float fx = a.flow[(n * 2 + 0) * hw + pix], fy = a.flow[(n * 2 + 1) * hw + pix];
+            bilinear_setup(fx, fy, a.gx[x], a.gy[y], a.H, a.W, a.align_corners, x0, y0, wx, wy);
+            wgt = a.weight[n * hw + pix];
+        }
+        const float m = a.fg ? a.mask[n * hw + pix] : 0.f;
+        for (int c = 0; c < a.C; ++c) {
+            const long long o = (n * a.C + c) * hw + pix;
+            float raw = a.img_raw[o];
+            float fin = raw;
+            if (do_warp) {
+                const float wv = bilinear_fetch(a.prev + (n * a.C + c) * hw, a.H, a.W, x0, y0, wx, wy);
+                if (a.img_warp) a.img_warp[o] = wv;
+                fin = raw * wgt + wv * (1.f - wgt);
+            }
+            if (a.fg) {
+                const float f = a.fg[o];
+                fin = f * m + fin * (1.f - m);
+                raw = f * m + raw * (1.f - m);
+                a.img_raw[o] = raw;
+            }
+            a.img_final[o] = fin;
+            float* w = win + c * hw + pix;
+            const long long sl = (long long)a.C * hw;
+            for (int k = 0; k + 1 < a.roll_slots; ++k) w[k * sl] = w[(k + 1) * sl];
+            w[(a.roll_slots - 1) * sl] = fin;
+        }
+    }
+}
+
+struct WarpPoolOp : Op {
+    WarpPoolArgs a;
+    int launch(hipStream_t s) override {
+        hipLaunchKernelGGL(warp_blend_pool_kernel, dim3(grid_for((long long)a.w.H * a.w.W), (unsigned)a.w.N), dim3(256), 0, s, a);
+        return check_launch();
+    }
+    const char* name() const override { return "warp_blend_pool"; }
+};
+
+// v2v_window_gather_pool / v2v_window_scatter_pool: dense [K][elems] <-> pool [row_slot[k]][elems], elems = slots * C * H * W
+// floats.  blockIdx.y is the row (one slot word per workgroup); VEC = 4 moves 16-byte vectors (the host picks it where elems is a
+// multiple of 4 and both bases are 16-byte aligned), VEC = 1 single floats.
+struct WindowPoolArgs { float* dst; const float* src; const int* row_slot; long long elems; int K, S; };
+
+template <int VEC, bool SCATTER>
+__global__ __launch_bounds__(256) void window_pool_copy_kernel(const WindowPoolArgs a) {
+    const long long k = (long long)blockIdx.y;
+    const int slot = a.row_slot[k];
+    if (slot < 0 || slot >= a.S) return;
+    const float* src = a.src + (SCATTER ? k : (long long)slot) * a.elems;
+    float* dst = a.dst + (SCATTER ? (long long)slot : k) * a.elems;
+    const long long nvec = a.elems / VEC;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += stride) {
+        if (VEC == 4) reinterpret_cast<float4*>(dst)[v] = reinterpret_cast<const float4*>(src)[v];
+        else          dst[v] = src[v];
+    }
+}
+
+struct WindowPoolOp : Op {
+    WindowPoolArgs a; bool scatter;
+    int launch(hipStream_t s) override {
+        const bool vec = a.elems % 4 == 0 && (((uintptr_t)a.dst | (uintptr_t)a.src) & 15) == 0;
+        const dim3 g(grid_for(vec ? a.elems / 4 : a.elems), (unsigned)a.K), b(256);
+        if (scatter) {
+            if (vec) hipLaunchKernelGGL((window_pool_copy_kernel<4, true>), g, b, 0, s, a);
+            else     hipLaunchKernelGGL((window_pool_copy_kernel<1, true>), g, b, 0, s, a);
+        } else {
+            if (vec) hipLaunchKernelGGL((window_pool_copy_kernel<4, false>), g, b, 0, s, a);
+            else     hipLaunchKernelGGL((window_pool_copy_kernel<1, false>), g, b, 0, s, a);
+        }
+        return check_launch();
+    }
+    const char* name() const override { return scatter ? "window_scatter_pool" : "window_gather_pool"; }
 };
 
 struct ResampleArgs { const float* img; const float* flow; float* out; const float* gx; const float* gy; int N, C, H, W, align_corners; };
@@ -1467,6 +1641,55 @@ extern "C" int v2v_window_roll_slots(float* window, const float* frame, const in
     return submit(std::move(op), stream);
 }
 
+extern "C" int v2v_warp_blend_pool(float* img_raw, const float* flow, const float* weight, const float* prev,
+                                   const float* fg, const float* mask, float* img_final, float* img_warp,
+                                   const float* gx, const float* gy, float* window, int32_t slots, const int32_t* mode,
+                                   const int32_t* row_slot, int32_t K, int32_t S, int32_t C, int32_t H, int32_t W,
+                                   int32_t align_corners, void* stream) {
+    if (!mode || !row_slot) { set_error("warp_blend_pool: null %s", !mode ? "mode" : "row_slot"); return V2V_EINVAL; }
+    if (!img_raw || !img_final || (flow && (!weight || !prev || !gx || !gy)) || (fg && !mask) || !window || slots < 1 ||
+        K < 1 || K > 65535 || S < 1 || C < 1 || H < 1 || W < 1) {
+        set_error("warp_blend_pool: bad argument"); return V2V_EINVAL;
+    }
+    // as v2v_warp_blend_roll_batch, against the WHOLE pool: any slot may be rolled by this launch
+    const float* wend = window + (long long)S * slots * C * H * W;
+    const long long frame = (long long)K * C * H * W;
+    auto overlaps = [&](const float* p) { return p && p + frame > window && p < wend; };
+    if (overlaps(prev) || overlaps(img_final) || overlaps(img_raw) || overlaps(fg)) {
+        set_error("warp_blend_pool: the pool must not overlap the gather source or the frame buffers"); return V2V_EINVAL;
+    }
+    auto op = std::make_unique<WarpPoolOp>();
+    op->a.w = WarpArgs{img_raw, flow, weight, prev, fg, mask, img_final, img_warp, gx, gy, K, C, H, W, align_corners};
+    op->a.w.roll = window; op->a.w.roll_slots = slots;
+    op->a.mode = mode; op->a.row_slot = row_slot; op->a.S = S;
+    return submit(std::move(op), stream);
+}
+
+static int window_pool_copy(const char* what, float* dst, const float* src, bool scatter, const int32_t* row_slot, int32_t K,
+                            int32_t S, int32_t slots, int32_t C, int32_t H, int32_t W, void* stream) {
+    if (!dst || !src || !row_slot || K < 1 || K > 65535 || S < 1 || slots < 1 || C < 1 || H < 1 || W < 1) {
+        set_error("%s: null pointer or bad argument", what); return V2V_EINVAL;
+    }
+    const long long elems = (long long)slots * C * H * W;
+    const float* dense = scatter ? src : dst; const float* pool = scatter ? dst : src;
+    if (dense + K * elems > pool && dense < pool + S * elems) {
+        set_error("%s: dense and pool must not overlap", what); return V2V_EINVAL;
+    }
+    auto op = std::make_unique<WindowPoolOp>();
+    op->a = WindowPoolArgs{dst, src, row_slot, elems, K, S}; op->scatter = scatter;
+    return submit(std::move(op), stream);
+}
+
+extern "C" int v2v_window_gather_pool(float* dense, const float* pool, const int32_t* row_slot, int32_t K, int32_t S, int32_t slots,
+                                      int32_t C, int32_t H, int32_t W, void* stream) {
+    return window_pool_copy("window_gather_pool", dense, pool, false, row_slot, K, S, slots, C, H, W, stream);
+}
+
+extern "C" int v2v_window_scatter_pool(float* pool, const float* dense, const int32_t* row_slot, int32_t K, int32_t S, int32_t slots,
+                                       int32_t C, int32_t H, int32_t W, void* stream) {
+    return window_pool_copy("window_scatter_pool", pool, dense, true, row_slot, K, S, slots, C, H, W, stream);
+}
+
 extern "C" int v2v_frame_prologue(const void* labels, const void* inst, int32_t in_u8, uint8_t* codes, float* mask,
                                   const int32_t* fg_labels_dev, int32_t n_fg, int32_t T, int32_t H, int32_t W, int32_t label_nc,
                                   const float* window, int32_t win_C, void* packed, int32_t c_stride, float* last, int32_t last_C,
@@ -1494,6 +1717,31 @@ extern "C" int v2v_frame_prologue_batch(const void* labels, const void* inst, in
     op->a = PrologueArgs{labels, inst, codes, mask, fg_labels_dev, n_fg, window, window ? packed : nullptr, window ? last : nullptr,
                          T, H, W, label_nc, win_C, c_stride, last_C};
     op->a.N = N;
+    op->dtype = dtype; op->in_u8 = in_u8;
+    return submit(std::move(op), stream);
+}
+
+extern "C" int v2v_frame_prologue_pool(const void* labels, const void* inst, int32_t in_u8, uint8_t* codes, float* mask,
+                                       const int32_t* fg_labels_dev, int32_t n_fg, int32_t K, int32_t T, int32_t H, int32_t W,
+                                       int32_t label_nc, const float* window, int32_t S, const int32_t* row_slot, int32_t win_C,
+                                       void* packed, int32_t c_stride, float* last, int32_t last_C, int32_t dtype, void* stream) {
+    const int vec = dtype == V2V_BF16 ? 8 : 4;
+    if (!row_slot || !window) { set_error("frame_prologue_pool: null %s", !row_slot ? "row_slot" : "window"); return V2V_EINVAL; }
+    if (K < 1 || K > 65535 || S < 1) { set_error("frame_prologue_pool: bad row count %d / pool size %d", K, S); return V2V_EINVAL; }
+    if (!labels || !codes || T < 1 || H < 1 || W < 1 || label_nc < 1 || label_nc > 126 || (in_u8 != 0 && in_u8 != 1) ||
+        (dtype != V2V_F32 && dtype != V2V_BF16) || n_fg < 0 || (mask && n_fg > 0 && !fg_labels_dev) ||
+        (in_u8 ? ((uintptr_t)inst & 3) != 0 : (((uintptr_t)labels | (uintptr_t)inst) & 3) != 0)) {
+        set_error("frame_prologue_pool: bad argument (label_nc <= 126)"); return V2V_EINVAL;
+    }
+    if (!packed || win_C < 1 || c_stride % vec != 0 || win_C > c_stride || ((uintptr_t)packed & 15) != 0 ||
+        (last && (last_C < 1 || last_C > win_C))) {
+        set_error("frame_prologue_pool: bad window pack argument"); return V2V_EINVAL;
+    }
+    auto op = std::make_unique<ProloguePoolOp>();
+    op->a.p = PrologueArgs{labels, inst, codes, mask, fg_labels_dev, n_fg, window, packed, last,
+                           T, H, W, label_nc, win_C, c_stride, last_C};
+    op->a.p.N = K;
+    op->a.row_slot = row_slot; op->a.S = S;
     op->dtype = dtype; op->in_u8 = in_u8;
     return submit(std::move(op), stream);
 }

@@ -808,12 +808,14 @@ class Engine:
         src.codes = codes
         return codes
 
-    def frame_prologue(self, src, H, W, fg_labels, want_mask, window=None, last_C=0):
+    def frame_prologue(self, src, H, W, fg_labels, want_mask, window=None, last_C=0, row_slot=None):
         """Head of an inference frame whose label stems all run as gather-sums, in one launch (v2v_frame_prologue): the codes of
         label_codes, the foreground mask of encode_labels and -- with `window`, planar fp32 (1, C, H, W) -- the NHWC pack of the
         previous-frame window plus an fp32 copy of its last `last_C` planes (the warp's gather source).  The one-hot encoding
         is neither allocated nor written: the returned Act has its shape (a meta tensor) and its LabelSource, which is all a
-        gather-sum stem reads.  Returns (x0, mask, packed Act or None, last or None)."""
+        gather-sum stem reads.  Returns (x0, mask, packed Act or None, last or None).
+        row_slot: int32 (N,) device tensor read by the launch when it runs (v2v_frame_prologue_pool; pool plans):
+        `window` is then the pool (S, C, H, W) and dense row n packs and copies from slot row_slot[n]."""
         labels, inst, T = src.labels, src.inst, src.T
         N = labels.shape[0] if labels.dim() == 4 else 1      # multi-stream plans: maps (N, T, H, W), window (N, C, H, W)
         u8 = labels.dtype == torch.uint8
@@ -821,7 +823,12 @@ class Engine:
             raise TypeError("uint8 label maps go with int32 instance maps")
         if not u8 and (labels.dtype != torch.float32 or (inst is not None and inst.dtype != torch.float32)):
             raise TypeError("label / instance maps must be fp32-encoded integers, or uint8 + int32")
-        if N > 1 and window is not None and window.shape[0] != N:
+        if row_slot is not None:
+            if (window is None or window.dim() != 4 or window.dtype != torch.float32 or not window.is_contiguous()
+                    or row_slot.dtype != torch.int32 or tuple(row_slot.shape) != (N,) or not row_slot.is_contiguous()):
+                raise ValueError("frame_prologue: a pooled head reads an fp32 pool (S, C, H, W) through int32 row_slot (N,)")
+            self._keep(row_slot)
+        elif N > 1 and window is not None and window.shape[0] != N:
             raise ValueError("frame_prologue: %d label streams, window of %d" % (N, window.shape[0]))
         per = src.label_nc + (1 if inst is not None else 0)
         codes = torch.empty((T, H, W) if N == 1 else (N, T, H, W), dtype=torch.uint8, device=self.device)
@@ -839,7 +846,12 @@ class Engine:
             cs = packed.Cs
             if last_C:
                 last = self.empty_f32(N, last_C, H, W)
-        if N == 1:
+        if row_slot is not None:
+            check(lib.v2v_frame_prologue_pool(_ptr(labels), _ptr(inst), int(u8), _ptr(codes), _ptr(mask), _ptr(fg),
+                                              0 if fg is None else fg.numel(), N, T, H, W, src.label_nc, _ptr(window),
+                                              window.shape[0], _ptr(row_slot), win_C, _ptr(packed.t), cs, _ptr(last), last_C,
+                                              self.dtype, _stream()), "frame_prologue_pool")
+        elif N == 1:
             check(lib.v2v_frame_prologue(_ptr(labels), _ptr(inst), int(u8), _ptr(codes), _ptr(mask), _ptr(fg),
                                          0 if fg is None else fg.numel(), T, H, W, src.label_nc, _ptr(window), win_C,
                                          _ptr(None if packed is None else packed.t), cs, _ptr(last), last_C, self.dtype, _stream()),
@@ -2048,12 +2060,14 @@ class Engine:
         self.label("avgpool3s2_planar")
         return out
 
-    def warp_blend(self, img_raw, flow, weight, prev, fg, mask, want_warp=False, roll=None, slot_mode=None):
+    def warp_blend(self, img_raw, flow, weight, prev, fg, mask, want_warp=False, roll=None, slot_mode=None, row_slot=None):
         """roll: the fp32 window (slots, C, H, W) of the last generated frames, oldest first -- the launch rolls it itself
         (v2v_warp_blend_roll; inference frame plans); (N, slots, C, H, W) for the N streams of a multi-stream plan
         (v2v_warp_blend_roll_batch).  `prev` must then be a buffer outside the window.
         slot_mode: int32 (N,) device tensor of per-stream modes (0 steady, 1 raw-only first frame, 2 idle), read by the launch
-        when it runs (v2v_warp_blend_slots; slot plans); roll is then (N, slots, C, H, W) or None."""
+        when it runs (v2v_warp_blend_slots; slot plans); roll is then (N, slots, C, H, W) or None.
+        row_slot: int32 (N,) device tensor, with slot_mode (0 or 1 only) and roll = the pool (S, slots, C, H, W): dense row n
+        rolls slot row_slot[n] (v2v_warp_blend_pool; pool plans)."""
         N, Cc, H, W = img_raw.shape
         if self._training() and any(t is not None and t.requires_grad for t in (img_raw, flow, weight, prev, fg)):
             from . import autograd as AG
@@ -2064,6 +2078,19 @@ class Engine:
         warp = self.empty_f32(N, Cc, H, W) if (want_warp and flow is not None) else None
         for t in (gx, gy):
             self._keep(t)
+        if row_slot is not None:
+            if (slot_mode is None or roll is None or roll.dim() != 5 or tuple(roll.shape[2:]) != (Cc, H, W)
+                    or roll.dtype != torch.float32 or not roll.is_contiguous()
+                    or any(t.dtype != torch.int32 or tuple(t.shape) != (N,) or not t.is_contiguous() for t in (slot_mode, row_slot))):
+                raise ValueError("warp_blend: a pooled blend rolls an fp32 pool (S, slots, C, H, W) under int32 slot_mode, row_slot (N,)")
+            self._keep(slot_mode)
+            self._keep(row_slot)
+            check(lib.v2v_warp_blend_pool(_ptr(img_raw), _ptr(flow), _ptr(weight), _ptr(prev), _ptr(fg), _ptr(mask),
+                                          _ptr(final), _ptr(warp), _ptr(gx), _ptr(gy), _ptr(roll), roll.shape[1], _ptr(slot_mode),
+                                          _ptr(row_slot), N, roll.shape[0], Cc, H, W, int(self.align_corners), _stream()),
+                  "warp_blend_pool")
+            self.label("warp_blend")
+            return final, warp
         if slot_mode is not None:
             if slot_mode.dtype != torch.int32 or tuple(slot_mode.shape) != (N,) or not slot_mode.is_contiguous():
                 raise ValueError("warp_blend: slot_mode is int32 (N,)")
@@ -2111,6 +2138,27 @@ class Engine:
         check(lib.v2v_window_roll_slots(_ptr(window), _ptr(frame), _ptr(slot_mode), N, slots, Cc, H, W, _stream()),
               "window_roll_slots")
         self.label("window_roll")
+
+    def _window_pool_args(self, dense, pool, row_slot, what):
+        K, S = dense.shape[0], pool.shape[0]
+        if (dense.dim() != 5 or pool.dim() != 5 or tuple(dense.shape[1:]) != tuple(pool.shape[1:]) or tuple(row_slot.shape) != (K,)
+                or row_slot.dtype != torch.int32 or dense.dtype != torch.float32 or pool.dtype != torch.float32
+                or not (dense.is_contiguous() and pool.is_contiguous() and row_slot.is_contiguous())):
+            raise ValueError("%s: fp32 dense (K, slots, C, H, W), fp32 pool (S, slots, C, H, W), int32 row_slot (K,)" % what)
+        self._keep(row_slot)
+        return (_ptr(row_slot), K, S) + tuple(dense.shape[1:]) + (_stream(),)
+
+    def window_gather(self, dense, pool, row_slot):
+        """dense (K, slots, C, H, W) <- pool[row_slot[k]] of the pool (S, slots, C, H, W), one launch (v2v_window_gather_pool)."""
+        check(lib.v2v_window_gather_pool(_ptr(dense), _ptr(pool), *self._window_pool_args(dense, pool, row_slot, "window_gather")),
+              "window_gather_pool")
+        self.label("window_gather")
+
+    def window_scatter(self, pool, dense, row_slot):
+        """pool[row_slot[k]] <- dense[k], the inverse of window_gather (v2v_window_scatter_pool); other slots are not touched."""
+        check(lib.v2v_window_scatter_pool(_ptr(pool), _ptr(dense), *self._window_pool_args(dense, pool, row_slot, "window_scatter")),
+              "window_scatter_pool")
+        self.label("window_scatter")
 
     def resample_flow(self, img, flow):
         N, Cc, H, W = img.shape

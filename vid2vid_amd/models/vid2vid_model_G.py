@@ -51,6 +51,18 @@ def nearest_face_features(feat_map, inst, features, feat_num):
     return out
 
 
+class _StreamPool:
+    """The windows of the S stream slots of a compacting model (opt.compact_streams): fake_B_prev per scale,
+    (S, tG-1, 3, h, w), owned by the model -- every pool plan of this resolution, whatever its row count K, reaches them through
+    its row_slot indices, so changing K between calls copies nothing.  `idle`: the slots whose rows of the tensors the last call
+    returned are zero."""
+
+    def __init__(self, S, tG, nc, H, W, n_scales, device):
+        self.S, self.H, self.W = S, H, W
+        self.windows = [torch.zeros(S, tG - 1, nc, H >> si, W >> si, dtype=torch.float32, device=device) for si in range(n_scales)]
+        self.idle = []
+
+
 class _FramePlan:
     """Buffers + launch sequence generating one frame at every spatial scale, for B independent sequences (streams) per
     replay.  B == 1: the buffers have no stream dimension, exactly the single-sequence plan.  B > 1: every static
@@ -58,15 +70,21 @@ class _FramePlan:
     stream b computes what a batch-1 plan computes on sequence b alone.
     slots (B > 1): the plan owns `slot_mode`, int32 (B,), refreshed per call -- 0 steady, 1 raw-only first frame,
     2 idle -- and its tail launches (v2v_warp_blend_slots, v2v_window_roll_slots) branch on it per stream; everything in front
-    of the tail runs for all B streams whatever their mode."""
+    of the tail runs for all B streams whatever their mode.
+    pool (a _StreamPool): the plan has B = K dense rows and serves K of the pool's S slots: `prev` IS the pool's
+    windows, row k works on slot row_slot[k] under row_mode[k] (0 steady, 1 raw-only first frame; int32 (K,), refreshed per call
+    like slot_mode).  K == 1 emits the batch-1 body, K > 1 the per-stream one; only the head and the tail know about slots."""
 
-    def __init__(self, model, H, W, in_ch, has_inst, use_raw_only, use_graph=True, u8=False, B=1, slots=False):
+    def __init__(self, model, H, W, in_ch, has_inst, use_raw_only, use_graph=True, u8=False, B=1, slots=False, pool=None):
         opt, eng = model.opt, model.engine
         self.model, self.eng = model, eng
         self.H, self.W, self.use_raw_only, self.B = H, W, use_raw_only, B
         self.slots = bool(slots)
         if self.slots and (B < 2 or use_raw_only):
             raise ValueError("a slot plan has B > 1 streams and decides raw-only frames per stream (slot_mode 1)")
+        self.pool = pool
+        if pool is not None and (self.slots or use_raw_only or not 1 <= B <= pool.S or (pool.H, pool.W) != (H, W)):
+            raise ValueError("a pool plan has 1..S rows at the pool's resolution and decides raw-only frames per row (row_mode 1)")
         lead = (B,) if B > 1 else ()
         tG, S = opt.n_frames_G, model.n_scales
         self.label_mode = opt.label_nc != 0
@@ -82,8 +100,11 @@ class _FramePlan:
             self.labels = self.inst = None
             self.raw_in = torch.zeros(B, tG * in_ch, H, W, dtype=torch.float32, device=dev)
         # fake_B_prev[si]: (tG-1, 3, h, w) per scale, si = 0 finest  (reference :228, :248-250); (B, tG-1, 3, h, w) at B > 1
-        self.prev = [torch.zeros(*lead, tG - 1, opt.output_nc, H >> si, W >> si, dtype=torch.float32, device=dev)
-                     for si in range(S)]
+        if pool is not None:
+            self.prev = pool.windows
+        else:
+            self.prev = [torch.zeros(*lead, tG - 1, opt.output_nc, H >> si, W >> si, dtype=torch.float32, device=dev)
+                         for si in range(S)]
         self.slot_mode = self.slot_mode_host = self._slot_mode_copied = None
         if self.slots:
             self.slot_mode = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -92,6 +113,16 @@ class _FramePlan:
                 self.slot_mode_host = self.slot_mode_host.pin_memory()
             # does the finest generator end in the blend launch (which writes an idle stream's row of zeros)?
             self.blend_launch = getattr(model, "netG" + str(S - 1)).blends_in_tail()
+        self.row_slot = self._rows = self._rows_host = None
+        if pool is not None:
+            # row_slot | row_mode in one buffer: one 8*K-byte copy per call.  Identity slots until the first call (the warm-up and
+            # tuning replays of _build run on valid, distinct slots; _frame_plan puts the windows back behind them)
+            self._rows = torch.cat([torch.arange(B, dtype=torch.int32), torch.zeros(B, dtype=torch.int32)]).to(dev)
+            self._rows_host = torch.zeros(2 * B, dtype=torch.int32)
+            if dev.type == "cuda":
+                self._rows_host = self._rows_host.pin_memory()
+            self.row_slot, self.slot_mode = self._rows[:B], self._rows[B:]
+            self.dense = {}              # si -> (K, tG-1, 3, h, w): the gathered windows of the paths off the rolling blend
         self.out = {}
         # independent towers / branches on parallel plan lanes (parallel hipGraph paths); opt.lanes or V2V_LANES
         self.lanes = bool(int(getattr(opt, "lanes", os.environ.get("V2V_LANES", "1")))) and use_graph
@@ -266,12 +297,15 @@ class _FramePlan:
             mask = masks[si]
             if opt.fg and mask is None:
                 mask = self._mask_from_pooled(x, per, tG)
-            prev_nchw = self.prev[si].view(B, -1, H >> si, W >> si)
+            window = self._gathered(si) if self.pool is not None else self.prev[si]
+            prev_nchw = window.view(B, -1, H >> si, W >> si)
             fake_B, flow, weight, raw, feat, flow_feat, fg_feat = netG.emit(
                 eng, x, eng.pack(prev_nchw), prev_nchw, mask, feat, flow_feat, fg_feat, self.use_raw_only,
                 tag="G%d" % s, slot_mode=self.slot_mode)
             # fake_B_prev[si] = cat(prev[1:], fake_B)   (:228)
-            self._roll(self.prev[si], fake_B)
+            self._roll(window, fake_B)
+            if self.pool is not None:
+                eng.window_scatter(self.prev[si], window, self.row_slot)
             self.out["flow%d" % si], self.out["weight%d" % si], self.out["raw%d" % si] = flow, weight, raw
         self.out["fake_B"] = fake_B
         # real_A[0][0, -1]: encoded last label frame, returned for visualisation (:209)
@@ -299,23 +333,45 @@ class _FramePlan:
         tG, H, W = opt.n_frames_G, self.H, self.W
         netG = m.netG0
         prev = self.prev[0]
-        x0, mask0, prev_act, last = eng.frame_prologue(src, H, W, opt.fg_labels, opt.fg, window=prev.view(self.B, -1, H, W),
-                                                       last_C=opt.output_nc)
+        rolls = netG.rolls_in_tail(self.use_raw_only)
+        row_slot = None
+        if self.pool is not None and rolls:
+            # head and tail reach the pool through row_slot: no copy of any window
+            row_slot = self.row_slot
+            x0, mask0, prev_act, last = eng.frame_prologue(src, H, W, opt.fg_labels, opt.fg, window=prev.view(self.pool.S, -1, H, W),
+                                                           last_C=opt.output_nc, row_slot=row_slot)
+        else:
+            if self.pool is not None:        # no blend launch to roll in: the dense lowering on gathered windows
+                prev = self._gathered(0)
+            x0, mask0, prev_act, last = eng.frame_prologue(src, H, W, opt.fg_labels, opt.fg, window=prev.view(self.B, -1, H, W),
+                                                           last_C=opt.output_nc)
 
         def real_A_last():
             self.out["real_A_last"] = self._real_A_last()
-        roll = prev if netG.rolls_in_tail(self.use_raw_only) else None
+        roll = prev if rolls else None
         fake_B, flow, weight, raw, _, _, _ = netG.emit(eng, x0, prev_act, last, mask0, None, None, None, self.use_raw_only,
                                                        tag="G0", roll=roll, side=real_A_last,
-                                                       slot_mode=self.slot_mode)
+                                                       slot_mode=self.slot_mode, row_slot=row_slot)
         if roll is None:
             self._roll(prev, fake_B)
+            if self.pool is not None:
+                eng.window_scatter(self.prev[0], prev, self.row_slot)
         self.out["flow0"], self.out["weight0"], self.out["raw0"] = flow, weight, raw
         self.out["fake_B"] = fake_B
         self.conv_log = list(eng.conv_log)
 
+    def _gathered(self, si):
+        """Pool plans off the rolling blend: the windows of this plan's rows at scale si as a dense (K, tG-1, 3, h, w) copy, by
+        one launch; the dense lowering runs on it and window_scatter puts it back."""
+        dense = self.dense.get(si)
+        if dense is None:
+            dense = self.dense[si] = torch.zeros((self.B,) + tuple(self.prev[si].shape[1:]), dtype=torch.float32,
+                                                 device=self.prev[si].device)
+        self.eng.window_gather(dense, self.prev[si], self.row_slot)
+        return dense
+
     def _roll(self, prev, fake_B):
-        if self.slots:                   # one launch under slot_mode: an idle stream's window is not touched
+        if self.slots or self.pool is not None:   # one launch under slot_mode: an idle stream's window is not touched
             self.eng.window_roll(prev, fake_B, self.slot_mode)
         elif self.B > 1:                 # (B, tG-1, 3, h, w) <- (B, 3, h, w): every stream rolls its own window
             for b in range(self.B):
@@ -342,6 +398,16 @@ class _FramePlan:
         self.slot_mode_host.copy_(torch.as_tensor(modes, dtype=torch.int32))
         self.slot_mode.copy_(self.slot_mode_host, non_blocking=True)
         if self.slot_mode.device.type == "cuda":
+            self._slot_mode_copied = torch.cuda.Event()
+            self._slot_mode_copied.record()
+
+    def set_rows(self, rows, modes):
+        """Pool plans: refresh row_slot and row_mode for the next replay, as set_slot_modes does (one asynchronous copy)."""
+        if self._slot_mode_copied is not None:
+            self._slot_mode_copied.synchronize()
+        self._rows_host.copy_(torch.as_tensor(list(rows) + list(modes), dtype=torch.int32))
+        self._rows.copy_(self._rows_host, non_blocking=True)
+        if self._rows.device.type == "cuda":
             self._slot_mode_copied = torch.cuda.Event()
             self._slot_mode_copied.record()
 
@@ -390,6 +456,7 @@ class Vid2VidModelG(BaseModel):
                 self.load_network(getattr(self, "netG" + str(s)), "G" + str(s), opt.which_epoch, opt.load_pretrain)
         self.netG_i = self.load_single_G() if self.use_single_G else None
         self._plans = {}
+        self._pools = {}
 
         if self.isTrain:
             self.n_gpus = opt.n_gpus_gen if opt.batchSize == 1 else 1
@@ -411,15 +478,43 @@ class Vid2VidModelG(BaseModel):
         self.bind_precision()
 
     # ------------------------------------------------------------------ inference
-    def _frame_plan(self, H, W, in_ch, has_inst, use_raw_only, u8=False, B=1, slots=False):
-        key = (H, W, in_ch, has_inst, use_raw_only, self.precision, u8, B) + (("slots",) if slots else ())
+    def _frame_plan(self, H, W, in_ch, has_inst, use_raw_only, u8=False, B=1, slots=False, pool=None):
+        """pool: the slot capacity S of a pool plan with B rows; its key ends in ("pool", S)."""
+        key = (H, W, in_ch, has_inst, use_raw_only, self.precision, u8, B) + (("slots",) if slots else ()) + \
+              ((("pool", pool),) if pool else ())
         fp = self._plans.get(key)
         if fp is None:
             self.engine.refresh_weights()
+            windows = self._stream_pool(pool, H, W) if pool else None
+            # building a plan replays it (warm-up, tile search): the live windows are put back behind that
+            saved = [w.clone() for w in windows.windows] if pool else []
             fp = _FramePlan(self, H, W, in_ch, has_inst, use_raw_only,
-                            use_graph=getattr(self.opt, "use_graph", True), u8=u8, B=B, slots=slots)
+                            use_graph=getattr(self.opt, "use_graph", True), u8=u8, B=B, slots=slots, pool=windows)
+            for w, keep in zip(windows.windows if pool else [], saved):
+                w.copy_(keep)
             self._plans[key] = fp
         return fp
+
+    def _stream_pool(self, S, H, W):
+        """The model's windows for S slots at H x W: allocated once, so the plans recorded against them stay valid across restarts."""
+        pool = self._pools.get((S, H, W))
+        if pool is None:
+            pool = self._pools[(S, H, W)] = _StreamPool(S, self.opt.n_frames_G, self.opt.output_nc, H, W, self.n_scales, self.device)
+        return pool
+
+    def prepare_streams(self, S, H, W, in_ch, has_inst, u8=False, counts=None):
+        """Build the pool plans (opt.compact_streams) of a server with S slots at H x W for the active counts in
+        `counts` (default 1..S) ahead of time: each plan records, and searches its tiles, when it is first built -- here rather
+        than in the first call that happens to have that many live clips.  in_ch, has_inst, u8: as the calls will have them
+        (channels of input_A, whether inst_A is given and used, uint8 label maps).  Activations cost one stream-size per row of
+        every plan built: S (S + 1) / 2 stream-sizes for all counts."""
+        counts = list(range(1, S + 1)) if counts is None else sorted(set(int(k) for k in counts))
+        if S < 2 or not counts or counts[0] < 1 or counts[-1] > S:
+            raise ValueError("prepare_streams: S >= 2 slots and active counts within 1..S")
+        with torch.no_grad():
+            for K in counts:
+                self._frame_plan(H, W, in_ch, bool(has_inst and self.opt.use_instance and self.opt.label_nc != 0), False, bool(u8),
+                                 B=K, pool=S)
 
     @staticmethod
     def _slot_set(arg, B, name):
@@ -458,7 +553,11 @@ class Vid2VidModelG(BaseModel):
         it continues where it paused.
         restart: the streams that begin a new sequence with this call: their windows are re-seeded by generate_first_frame on
         their rows alone (input_B rows of the other streams are ignored).  restart implies active; a stream that is restarted
-        and idle, an index outside [0, B) or a mask of another length is a ValueError."""
+        and idle, an index outside [0, B) or a mask of another length is a ValueError.
+        opt.compact_streams (read per call): with B > 1 the call replays a plan with one row per active stream, on
+        windows the model owns; the contract above is unchanged.  Setting it while sequences run outside a pool is a ValueError
+        (assign fake_B_prev = None with it); clearing it while sequences run continues them, the pool's windows being copied
+        once into the slot or plain plan's own."""
         opt = self.opt
         tG = opt.n_frames_G
         with torch.no_grad():
@@ -477,9 +576,11 @@ class Vid2VidModelG(BaseModel):
                     raise ValueError("inference: stream(s) %s are restarted and idle in the same call" % both)
             self._check_device_status()
             self.is_first_frame = not hasattr(self, "fake_B_prev") or self.fake_B_prev is None
-            if not self.is_first_frame and self._active_plan is not None and self._active_plan.B != B:
-                raise ValueError("inference: %d sequence(s) given while %d are running; assign fake_B_prev = None to restart"
-                                 % (B, self._active_plan.B))
+            if not self.is_first_frame and self._active_plan is not None:
+                running = self._active_plan.B if self._active_plan.pool is None else self._active_plan.pool.S
+                if running != B:
+                    raise ValueError("inference: %d sequence(s) given while %d are running; assign fake_B_prev = None to restart"
+                                     % (B, running))
             has_inst = bool(opt.use_instance and inst_A is not None and opt.label_nc != 0)
             if slot_call and B == 1:
                 # one stream needs no slot plan: idle is no call at all, a restart is fake_B_prev = None
@@ -496,6 +597,10 @@ class Vid2VidModelG(BaseModel):
             if slot_call:
                 self._slots_on = True            # sticky until fake_B_prev = None
             u8 = bool(opt.label_nc != 0 and input_A.dtype == torch.uint8)
+            if B > 1 and getattr(opt, "compact_streams", False):
+                if not slot_call:
+                    act, rst = [True] * B, [False] * B
+                return self._inference_pool(input_A, input_B, inst_A, act, rst, has_inst, u8)
             if self._slots_on:
                 if not slot_call:
                     act, rst = [True] * B, [False] * B
@@ -567,6 +672,59 @@ class Vid2VidModelG(BaseModel):
         if not fp.blend_launch and len(rows) != B:        # no blend launch in this generator: nothing wrote the idle rows' zeros
             fake[[b for b in range(B) if not act[b]]] = 0
         return fake, fp.out["real_A_last"].clone()
+
+    def _inference_pool(self, input_A, input_B, inst_A, act, rst, has_inst, u8):
+        """One call of a compacting model (opt.compact_streams, B = S > 1 slots): the contract of _inference_slots,
+        by a replay of the pool plan that has one row per ACTIVE stream -- row k runs slot rows[k], rows ascending."""
+        opt, dev = self.opt, self.device
+        tG = opt.n_frames_G
+        S, _, in_ch, H, W = input_A.shape
+        rows = [b for b in range(S) if act[b]]
+        K = len(rows)
+        last_C = in_ch if opt.label_nc == 0 else opt.label_nc + int(has_inst)
+        fake = torch.zeros(S, opt.output_nc, H, W, dtype=torch.float32, device=dev)
+        real_A_last = torch.zeros(S, last_C, H, W, dtype=torch.float32, device=dev)
+        if K == 0:                      # nothing is live: no replay, no state touched
+            return fake, real_A_last
+        pool = self._stream_pool(S, H, W)
+        if not self.is_first_frame and (self._active_plan is None or self._active_plan.pool is not pool):
+            raise ValueError("inference: the running sequences are not in a %d-slot pool at %dx%d; assign fake_B_prev = None "
+                             "to restart" % (S, W, H))
+        fp = self._frame_plan(H, W, in_ch, has_inst, False, u8, B=K, pool=S)
+        if self.is_first_frame:
+            rst = list(act)
+            for w in pool.windows:
+                w.zero_()
+        # ---- stage the rows of the active streams straight into the dense rows; an idle stream's rows are not read ----
+        sel = rows[0] if K == 1 else (slice(None) if K == S else rows)
+        if fp.label_mode:
+            fp.labels.copy_(input_A[sel, :tG, 0].to(dev, fp.labels.dtype, non_blocking=True))
+            if has_inst:
+                fp.inst.copy_(inst_A[sel, :tG, 0].to(dev, fp.inst.dtype, non_blocking=True))
+        else:
+            fp.raw_in.copy_(input_A[sel, :tG].reshape(fp.raw_in.shape).to(dev, torch.float32, non_blocking=True))
+        # ---- windows: a restarted slot is re-seeded on its rows alone ----
+        new = [b for b in range(S) if rst[b]]
+        if new:
+            first = self.generate_first_frame(input_A[new], None if input_B is None else input_B[new],
+                                              None if inst_A is None else inst_A[new])
+            for si in range(self.n_scales):
+                if len(new) == 1:
+                    pool.windows[si][new[0]].copy_(first[si])
+                else:
+                    for k, b in enumerate(new):
+                        pool.windows[si][b].copy_(first[si][k])
+        fp.set_rows(rows, [1 if (rst[b] and opt.no_first_img) else 0 for b in rows])
+        pool.idle = [b for b in range(S) if not act[b]]
+        self._active_plan = fp
+        self.fake_B_prev = pool.windows
+        fp.run()
+        # one indexed copy of the dense rows into the zero tensors: fresh tensors per frame, idle rows zero
+        index = fp.row_slot.long()
+        fake.index_copy_(0, index, fp.out["fake_B"])
+        last = fp.out["real_A_last"]
+        real_A_last.index_copy_(0, index, last if K > 1 else last.unsqueeze(0))
+        return fake, real_A_last
 
     def _check_device_status(self):
         """Kernels cannot return errors; the library's host-visible status word says whether a fused-norm spin barrier of

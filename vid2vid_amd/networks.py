@@ -249,11 +249,13 @@ class BaseNetwork(nn.Module):
         """Does emit end in the warp / blend launch?  (Without one the generated frame IS the image head's output.)"""
         return not (use_raw_only or self.no_flow) or self.use_fg_model
 
-    def _tail(self, eng, img_raw, flow, weight, img_prev_nchw, img_fg, mask, use_raw_only, roll=None, slot_mode=None):
+    def _tail(self, eng, img_raw, flow, weight, img_prev_nchw, img_fg, mask, use_raw_only, roll=None, slot_mode=None,
+              row_slot=None):
         """models/networks.py:215-230 / :309-323 as one fused launch.  roll: the frame plan's window of generated frames, rolled
         by that launch (Engine.warp_blend); img_prev_nchw is then a buffer of its own.
         slot_mode: per-stream modes of a slot plan -- the blend launch decides per stream between the steady
-        frame, the raw-only first frame and an idle row of zeros; use_raw_only is then False."""
+        frame, the raw-only first frame and an idle row of zeros; use_raw_only is then False.
+        row_slot: per-row slot indices of a pool plan -- roll is then the whole pool and row n rolls its slot."""
         do_warp = not (use_raw_only or self.no_flow)
         if not do_warp and img_fg is None:
             if roll is not None:
@@ -266,7 +268,8 @@ class BaseNetwork(nn.Module):
         if mask is not None:
             mask = mask.contiguous().float()
         res, _ = eng.warp_blend(img_raw, flow if do_warp else None, weight if do_warp else None, prev3,
-                                img_fg, mask if img_fg is not None else None, roll=roll, slot_mode=slot_mode)
+                                img_fg, mask if img_fg is not None else None, roll=roll, slot_mode=slot_mode,
+                                row_slot=row_slot)
         if isinstance(res, tuple):          # training graph: (img_final, blended img_raw), inputs untouched
             return res
         return res, img_raw                 # inference: img_raw was blended in place
@@ -349,9 +352,9 @@ class CompositeGenerator(BaseNetwork):
         return convs
 
     def emit(self, eng, x, prev, img_prev_nchw, mask, img_feat_coarse, flow_feat_coarse, img_fg_feat_coarse,
-             use_raw_only, tag="G0", roll=None, side=None, slot_mode=None):
+             use_raw_only, tag="G0", roll=None, side=None, slot_mode=None, row_slot=None):
         """x: Act labels (NHWC), prev: Act previous frames (NHWC), img_prev_nchw: fp32 planar.
-        roll, slot_mode: see _tail (rolls_in_tail says whether this configuration has the launch that does it).
+        roll, slot_mode, row_slot: see _tail (rolls_in_tail says whether this configuration has the launch that does it).
         side: a callable that emits launches nothing here depends on (the frame plan's real_A_last): called behind the
         foreground tower, on its lane -- the one furthest off the frame's critical path -- or in front of the tail without one.
         The label tower, the image tower and the foreground tower are independent until they are summed / blended, and
@@ -456,7 +459,7 @@ class CompositeGenerator(BaseNetwork):
             if self.use_fg_model:
                 eng.join(2)
         img_final, img_raw = self._tail(eng, img_raw, flow, weight, img_prev_nchw, img_fg, mask, use_raw_only, roll=roll,
-                                        slot_mode=slot_mode)
+                                        slot_mode=slot_mode, row_slot=row_slot)
         return img_final, flow, weight, img_raw, img_feat, flow_feat, img_fg_feat
 
     def rolls_in_tail(self, use_raw_only):

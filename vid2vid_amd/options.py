@@ -29,6 +29,7 @@ _DEFAULTS = dict(
     vgg19_checkpoint="checkpoints/vgg19-dcbb9e9d.pth",   # torchvision's vgg19 state_dict (the reference downloads it)
     fix_update_fixed_params=False,   # True: update_fixed_params rebuilds the captured optimizer over all scales (the reference's
                                      # evident intent); False: the reference's observable behaviour (models/base_model.py docstring)
+    compact_streams=False,    # multi-stream inference replays a plan with one row per ACTIVE stream (stream pool)
 )
 
 
