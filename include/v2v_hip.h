@@ -750,6 +750,17 @@ int v2v_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
 int v2v_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                       float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                       void* state, void* stream);
+/* Both updates with an exponential moving average of the weights kept in the same pass: param, exp_avg and
+ * exp_avg_sq get the bits of v2v_adam_step / v2v_adam_step_dev, then ema[i] = fma(ema_decay, ema[i], (1 - ema_decay) * param[i])
+ * with the NEW param[i] (1 - ema_decay is rounded once, from double).  ema: n floats that overlap none of the other buffers;
+ * ema_decay in [0, 1] (0: ema becomes a copy of param, 1: ema is left as it is).  Where all five buffers share their
+ * misalignment to 16 bytes the data moves as 16-byte vectors. */
+int v2v_adam_step_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                      float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                      int32_t step, float ema_decay, void* stream);
+int v2v_adam_step_dev_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                          float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                          void* state, float ema_decay, void* stream);
 int v2v_memset_zero(void* p, int64_t bytes, void* stream);
 
 /* ---- plan executor: a recorded launch sequence replayed as one call / one hipGraph ---- */

@@ -186,6 +186,93 @@ struct AdamOp : Op {
     const char* name() const override { return "adam_step"; }
 };
 
+// ---- Adam + weight averaging -----------------------------------------------
+// The same update, plus a shadow of the weights in the same pass: ema = decay * ema + (1 - decay) * p'.  One kernel serves both
+// forms (DEV: step count / learning rate in device memory, behind the same tick launch).  [head, head + 4 * nvec) is the part
+// of [0, n) where all five buffers are 16-byte aligned (nvec = 0 when their misalignments differ): it moves as float4, the
+// head and the tail as scalars.
+struct AdamEmaArgs {
+    float* p; const float* g; float* m; float* v; float* e; AdamDevState* st;
+    long long n, head, nvec;
+    float lr, b1, b2, eps, bc1, bc2_sqrt, wd, gscale, decay, omd;
+};
+struct AdamEmaCoef { float step_size, bc2_sqrt, b1, b2, omb1, omb2, eps, wd, gscale, decay, omd; };
+
+// adam_step_kernel / adam_step_dev_kernel compile to separately rounded multiplies and adds everywhere except the last line,
+// p - step_size * (m / denom), which is one fused multiply-add.  Contraction is switched off here and that one fma is written
+// out, so these bits do not depend on what the optimiser makes of a wider loop body.
+__device__ __forceinline__ void adam_ema_elem(float& p, float g, float& m, float& v, float& e, const AdamEmaCoef& c) {
+#pragma clang fp contract(off)
+    g = g * c.gscale;
+    if (c.wd != 0.f) { const float t = c.wd * p; g = g + t; }
+    const float m0 = c.b1 * m, m1 = c.omb1 * g;
+    const float v0 = c.b2 * v, v1 = c.omb2 * g * g;
+    m = m0 + m1; v = v0 + v1;
+    const float denom = sqrtf(v) / c.bc2_sqrt + c.eps;
+    p = fmaf(-c.step_size, m / denom, p);
+    const float q = c.omd * p;
+    e = fmaf(c.decay, e, q);
+}
+
+template <bool DEV>
+__global__ __launch_bounds__(256) void adam_step_ema_kernel(const AdamEmaArgs a) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const long long t0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    AdamEmaCoef c;
+    if (DEV) {
+        const int step = a.st->step;
+        const double bc1 = 1.0 - pow((double)a.b1, (double)step);    // adam_step_dev_kernel's prologue
+        const double bc2 = 1.0 - pow((double)a.b2, (double)step);
+        c.step_size = a.st->lr / (float)bc1;
+        c.bc2_sqrt = (float)sqrt(bc2);
+    } else {
+        c.step_size = a.lr / a.bc1;
+        c.bc2_sqrt = a.bc2_sqrt;
+    }
+    c.b1 = a.b1; c.b2 = a.b2; c.omb1 = 1.f - a.b1; c.omb2 = 1.f - a.b2;
+    c.eps = a.eps; c.wd = a.wd; c.gscale = a.gscale; c.decay = a.decay; c.omd = a.omd;
+
+    const long long vbase = a.head;
+    for (long long k = t0; k < a.nvec; k += stride) {
+        const long long i = vbase + 4 * k;
+        float4 p = *reinterpret_cast<const float4*>(a.p + i);
+        const float4 g = *reinterpret_cast<const float4*>(a.g + i);
+        float4 m = *reinterpret_cast<const float4*>(a.m + i);
+        float4 v = *reinterpret_cast<const float4*>(a.v + i);
+        float4 e = *reinterpret_cast<const float4*>(a.e + i);
+        adam_ema_elem(p.x, g.x, m.x, v.x, e.x, c);
+        adam_ema_elem(p.y, g.y, m.y, v.y, e.y, c);
+        adam_ema_elem(p.z, g.z, m.z, v.z, e.z, c);
+        adam_ema_elem(p.w, g.w, m.w, v.w, e.w, c);
+        *reinterpret_cast<float4*>(a.m + i) = m;
+        *reinterpret_cast<float4*>(a.v + i) = v;
+        *reinterpret_cast<float4*>(a.p + i) = p;
+        *reinterpret_cast<float4*>(a.e + i) = e;
+    }
+    const long long nscalar = a.n - 4 * a.nvec;          // head, then the tail behind the vector part
+    for (long long j = t0; j < nscalar; j += stride) {
+        const long long i = j < a.head ? j : j + 4 * a.nvec;
+        float p = a.p[i], m = a.m[i], v = a.v[i], e = a.e[i];
+        adam_ema_elem(p, a.g[i], m, v, e, c);
+        a.m[i] = m; a.v[i] = v; a.p[i] = p; a.e[i] = e;
+    }
+}
+
+struct AdamEmaOp : Op {
+    AdamEmaArgs a; bool dev;
+    int launch(hipStream_t s) override {
+        long long b = ceil_div(a.n, 256 * 4); if (b > 8192) b = 8192; if (b < 1) b = 1;
+        if (dev) {
+            hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, s, a.st);
+            hipLaunchKernelGGL(adam_step_ema_kernel<true>, dim3((unsigned)b), dim3(256), 0, s, a);
+        } else {
+            hipLaunchKernelGGL(adam_step_ema_kernel<false>, dim3((unsigned)b), dim3(256), 0, s, a);
+        }
+        return check_launch();
+    }
+    const char* name() const override { return dev ? "adam_step_dev_ema" : "adam_step_ema"; }
+};
+
 struct MemsetOp : Op {
     void* p; size_t bytes;
     int launch(hipStream_t s) override {
@@ -266,6 +353,62 @@ extern "C" int v2v_adam_step_dev(float* param, const float* grad, float* exp_avg
     if (!param || !grad || !exp_avg || !exp_avg_sq || n <= 0 || !state) { set_error("adam (device state): bad argument"); return V2V_EINVAL; }
     auto op = std::make_unique<AdamDevOp>();
     op->a = AdamDevArgs{param, grad, exp_avg, exp_avg_sq, n, beta1, beta2, eps, weight_decay, grad_scale, reinterpret_cast<AdamDevState*>(state)};
+    return submit(std::move(op), stream);
+}
+
+// Argument checks and the vector split shared by the two weight-averaging entry points.
+static int adam_ema_common(AdamEmaArgs& a, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema,
+                           int64_t n, float ema_decay) {
+    if (!param || !grad || !exp_avg || !exp_avg_sq || n <= 0) { set_error("adam (ema): bad argument"); return V2V_EINVAL; }
+    if (!ema) { set_error("adam (ema): null ema buffer"); return V2V_EINVAL; }
+    if (!(ema_decay >= 0.f && ema_decay <= 1.f)) { set_error("adam (ema): ema_decay %g outside [0, 1]", (double)ema_decay); return V2V_EINVAL; }
+    const void* bufs[5] = {param, grad, exp_avg, exp_avg_sq, ema};
+    const uintptr_t e0 = (uintptr_t)ema, bytes = (uintptr_t)n * 4;
+    for (int k = 0; k < 4; ++k) {
+        const uintptr_t x0 = (uintptr_t)bufs[k];
+        if (e0 < x0 + bytes && x0 < e0 + bytes) { set_error("adam (ema): the ema buffer overlaps another buffer"); return V2V_EINVAL; }
+    }
+    memset(&a, 0, sizeof(a));
+    a.p = param; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.e = ema; a.n = n;
+    const uintptr_t mis = e0 & 15;
+    bool same = (mis & 3) == 0;
+    for (int k = 0; k < 4; ++k) same = same && ((uintptr_t)bufs[k] & 15) == mis;
+    if (same) {
+        a.head = (long long)((16 - mis) & 15) / 4;
+        if (a.head > n) a.head = n;
+        a.nvec = (n - a.head) / 4;
+    }
+    a.decay = ema_decay;
+    a.omd = (float)(1.0 - (double)ema_decay);
+    return 0;
+}
+
+// v2v_adam_step plus ema = ema_decay * ema + (1 - ema_decay) * param' in the same pass
+extern "C" int v2v_adam_step_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                                 float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                                 int32_t step, float ema_decay, void* stream) {
+    auto op = std::make_unique<AdamEmaOp>();
+    int rc = adam_ema_common(op->a, param, grad, exp_avg, exp_avg_sq, ema, n, ema_decay);
+    if (rc) return rc;
+    if (step < 1) { set_error("adam (ema): bad argument"); return V2V_EINVAL; }
+    const double bc1 = 1.0 - pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+    op->a.lr = lr; op->a.b1 = beta1; op->a.b2 = beta2; op->a.eps = eps; op->a.bc1 = (float)bc1; op->a.bc2_sqrt = (float)sqrt(bc2);
+    op->a.wd = weight_decay; op->a.gscale = grad_scale;
+    op->dev = false;
+    return submit(std::move(op), stream);
+}
+
+extern "C" int v2v_adam_step_dev_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                                     float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                                     void* state, float ema_decay, void* stream) {
+    auto op = std::make_unique<AdamEmaOp>();
+    int rc = adam_ema_common(op->a, param, grad, exp_avg, exp_avg_sq, ema, n, ema_decay);
+    if (rc) return rc;
+    if (!state) { set_error("adam (ema, device state): bad argument"); return V2V_EINVAL; }
+    op->a.b1 = beta1; op->a.b2 = beta2; op->a.eps = eps; op->a.wd = weight_decay; op->a.gscale = grad_scale;
+    op->a.st = reinterpret_cast<AdamDevState*>(state);
+    op->dev = true;
     return submit(std::move(op), stream);
 }
 

@@ -452,8 +452,10 @@ class Vid2VidModelG(BaseModel):
         print("---------- Networks initialized -------------")
 
         if not self.isTrain or opt.continue_train or opt.load_pretrain:
+            # opt.use_ema (inference): serve the averaged weights a run with opt.ema_decay saved beside the raw ones
+            label = "G%d_ema" if (not self.isTrain and getattr(opt, "use_ema", False)) else "G%d"
             for s in range(self.n_scales):
-                self.load_network(getattr(self, "netG" + str(s)), "G" + str(s), opt.which_epoch, opt.load_pretrain)
+                self.load_network(getattr(self, "netG" + str(s)), label % s, opt.which_epoch, opt.load_pretrain)
         self.netG_i = self.load_single_G() if self.use_single_G else None
         self._plans = {}
         self._pools = {}
@@ -474,8 +476,28 @@ class Vid2VidModelG(BaseModel):
                 beta1, beta2, lr = 0, 0.9, opt.lr / 2
             else:
                 beta1, beta2, lr = opt.beta1, 0.999, opt.lr
-            self.optimizer_G = FusedAdam(params, lr=lr, betas=(beta1, beta2))
+            ema_decay = float(getattr(opt, "ema_decay", 0.0) or 0.0)
+            if ema_decay > 0.0:
+                self.optimizer_G = FusedAdam(params, lr=lr, betas=(beta1, beta2), ema_decay=ema_decay)
+                if opt.continue_train or opt.load_pretrain:
+                    self._load_ema(opt)
+            else:
+                self.optimizer_G = FusedAdam(params, lr=lr, betas=(beta1, beta2))
         self.bind_precision()
+
+    def _load_ema(self, opt):
+        """Resume the averaged weights of each scale from '<epoch>_net_G<s>_ema.pth' where that file exists; a scale without
+        one keeps the shadow FusedAdam starts with, a copy of the weights just loaded."""
+        views = self.optimizer_G.ema_views()
+        for s in range(self.n_scales):
+            path = self._ckpt_path("G%d_ema" % s, opt.which_epoch, opt.load_pretrain)
+            if not os.path.isfile(path):
+                continue
+            saved = torch.load(path, map_location="cpu")
+            with torch.no_grad():
+                for name, p in getattr(self, "netG" + str(s)).named_parameters():
+                    if p in views and name in saved and saved[name].shape == p.shape:
+                        views[p].copy_(saved[name])
 
     # ------------------------------------------------------------------ inference
     def _frame_plan(self, H, W, in_ch, has_inst, use_raw_only, u8=False, B=1, slots=False, pool=None):
@@ -945,6 +967,15 @@ class Vid2VidModelG(BaseModel):
     def save(self, label):
         for s in range(self.n_scales):
             self.save_network(getattr(self, "netG" + str(s)), "G" + str(s), label, self.gpu_ids)
+        # averaged weights (opt.ema_decay): '<label>_net_G<s>_ema.pth' for every scale the STEPPING optimizer holds --
+        # after the reference-compatible update_fixed_params that is _optimizer_G_live, not the stand-in in optimizer_G
+        live = getattr(self, "_optimizer_G_live", getattr(self, "optimizer_G", None))
+        if getattr(live, "ema_decay", 0.0) > 0.0:
+            views = live.ema_views()
+            for s in range(self.n_scales):
+                net = getattr(self, "netG" + str(s))
+                if any(p in views for p in net.parameters()):
+                    torch.save(live.ema_state_dict(net), self._ckpt_path("G%d_ema" % s, label))
 
     _active_plan = None
     _slots_on = False

@@ -77,8 +77,11 @@ class FlatBuffers:
 
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=2e-4, betas=(0.5, 0.999), eps=1e-8, weight_decay=0.0, grad_sync=None):
+    def __init__(self, params, lr=2e-4, betas=(0.5, 0.999), eps=1e-8, weight_decay=0.0, grad_sync=None, ema_decay=None):
         params = list(params)
+        ema_decay = float(ema_decay or 0.0)
+        if not 0.0 <= ema_decay <= 1.0:              # (NaN fails both comparisons)
+            raise ValueError("FusedAdam: ema_decay must lie in [0, 1], got %r" % ema_decay)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         if len(self.param_groups) != 1:
             raise NotImplementedError("FusedAdam keeps one flat buffer: pass a single parameter list")
@@ -100,6 +103,13 @@ class FusedAdam(torch.optim.Optimizer):
         # its step() -- and before its first step, when .grad is still what torch would hold.  Off: torch's semantics exactly
         # (gradients accumulate whenever a backward pass reaches the parameter).
         self.discard_stale_grads = False
+        # weight averaging, off unless ema_decay > 0: `ema` shadows flat_param (same layout, FlatBuffers.offsets)
+        # and is updated by the step's own kernel (v2v_adam_step_ema / v2v_adam_step_dev_ema).  With it off the object has no
+        # `ema` attribute at all and steps through the plain entry points.  Multi-rank: no all-reduce of the shadow -- all
+        # ranks hold equal weights and apply equal updates (the gradient IS all-reduced), so their shadows are equal too.
+        self.ema_decay = ema_decay
+        if ema_decay > 0.0:
+            self.ema = self.flat.flat_param.clone()
 
     def rebuild(self, params, lr=None, betas=None):
         """Re-home a (larger) parameter list in fresh flat buffers IN PLACE: same optimizer object, same grad_sync,
@@ -114,8 +124,16 @@ class FusedAdam(torch.optim.Optimizer):
         if betas is not None:
             grp["betas"] = tuple(betas)
         had_ready = self.flat.ready is not None
+        # the shadow values of parameters that were already tracked travel by parameter identity; new ones start from their weights
+        kept = {id(p): v.clone() for p, v in self.ema_views().items()} if self.ema_decay > 0.0 else {}
         self.flat = FlatBuffers(params)
         self.flat.owner_key = id(self)
+        if self.ema_decay > 0.0:
+            self.ema = self.flat.flat_param.clone()
+            with torch.no_grad():
+                for p, view in self.ema_views().items():
+                    if id(p) in kept:
+                        view.copy_(kept[id(p)])
         if had_ready and self.grad_sync is not None:
             from .parallel import BucketReady
             self.flat.ready = BucketReady(self.flat, self.grad_sync)
@@ -157,9 +175,13 @@ class FusedAdam(torch.optim.Optimizer):
         """Flat moments + step count + hyper-parameters.  The layout is the parameter order of this optimizer
         (FlatBuffers.offsets), so a checkpoint is valid for the same network definition."""
         grp = self.param_groups[0]
-        return {"step": self.device_step(), "exp_avg": self.exp_avg.detach().cpu().clone(),
-                "exp_avg_sq": self.exp_avg_sq.detach().cpu().clone(), "numel": self.flat.numel,
-                "hyper": {k: grp[k] for k in ("lr", "betas", "eps", "weight_decay")}}
+        state = {"step": self.device_step(), "exp_avg": self.exp_avg.detach().cpu().clone(),
+                 "exp_avg_sq": self.exp_avg_sq.detach().cpu().clone(), "numel": self.flat.numel,
+                 "hyper": {k: grp[k] for k in ("lr", "betas", "eps", "weight_decay")}}
+        if self.ema_decay > 0.0:
+            state["ema"] = self.ema.detach().cpu().clone()
+            state["ema_decay"] = self.ema_decay
+        return state
 
     def load_state_dict(self, state):
         if int(state["numel"]) != self.flat.numel:
@@ -169,10 +191,45 @@ class FusedAdam(torch.optim.Optimizer):
         with torch.no_grad():
             self.exp_avg.copy_(state["exp_avg"])
             self.exp_avg_sq.copy_(state["exp_avg_sq"])
+            if self.ema_decay > 0.0:                 # an optimizer built without ema_decay ignores a checkpoint's shadow
+                if state.get("ema") is not None:
+                    self.ema.copy_(state["ema"])
+                    self.ema_decay = float(state.get("ema_decay", self.ema_decay))
+                else:
+                    self.ema.copy_(self.flat.flat_param)     # checkpoint from a run without averaging: start from the weights
         for k, v in state.get("hyper", {}).items():
             self.param_groups[0][k] = tuple(v) if k == "betas" else v
         if self.capturable:
             self.make_capturable()                   # re-seed the device words from the restored count / learning rate
+
+    # ---- weight averaging ----
+    def ema_views(self):
+        """{parameter: view of `ema` with the parameter's shape}, in the optimizer's parameter order."""
+        if self.ema_decay <= 0.0:
+            raise RuntimeError("FusedAdam: weight averaging is off (ema_decay=None)")
+        f = self.flat
+        return {p: f._view(self.ema, p, o) for p, o in zip(f.params, f.offsets)}
+
+    def seed_ema(self, params=None):
+        """Restart the shadow of `params` (default: all tracked parameters) from their current weights, e.g. after a
+        checkpoint was loaded into the network behind the optimizer's back."""
+        views = self.ema_views()
+        with torch.no_grad():
+            for p in (views if params is None else params):
+                if p in views:
+                    views[p].copy_(p.data)
+
+    def ema_state_dict(self, network):
+        """`network.state_dict()` with every tracked parameter replaced by its shadow; untracked parameters and buffers pass
+        through.  CPU, contiguous: what BaseModel.save_network writes, key for key."""
+        if self.grad_sync is not None:
+            self.grad_sync.wait_pending(owner=self)  # an overlapped step still writes the shadow on the side stream
+        views = self.ema_views()
+        shadow = {name: views[p] for name, p in network.named_parameters() if p in views}
+        out = {}
+        for k, v in network.state_dict().items():
+            out[k] = shadow.get(k, v).detach().cpu().contiguous()
+        return out
 
     def zero_grad(self, set_to_none=False):
         from .lib import lib, check
@@ -206,6 +263,21 @@ class FusedAdam(torch.optim.Optimizer):
             sptr = None
             if f.flat_param.is_cuda:
                 sptr = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+            if self.ema_decay > 0.0:
+                ema = C.c_void_p(self.ema.data_ptr())
+                if self.capturable:
+                    self.sync_hyper()
+                    check(lib.v2v_adam_step_dev_ema(C.c_void_p(f.flat_param.data_ptr()), C.c_void_p(f.flat_grad.data_ptr()),
+                                                    C.c_void_p(self.exp_avg.data_ptr()), C.c_void_p(self.exp_avg_sq.data_ptr()),
+                                                    ema, f.numel, float(b1), float(b2), float(grp["eps"]),
+                                                    float(grp["weight_decay"]), float(gscale),
+                                                    C.c_void_p(self._dev_state.data_ptr()), self.ema_decay, sptr), "adam_step_dev_ema")
+                    return
+                check(lib.v2v_adam_step_ema(C.c_void_p(f.flat_param.data_ptr()), C.c_void_p(f.flat_grad.data_ptr()),
+                                            C.c_void_p(self.exp_avg.data_ptr()), C.c_void_p(self.exp_avg_sq.data_ptr()),
+                                            ema, f.numel, float(grp["lr"]), float(b1), float(b2), float(grp["eps"]),
+                                            float(grp["weight_decay"]), float(gscale), step_no, self.ema_decay, sptr), "adam_step_ema")
+                return
             if self.capturable:
                 self.sync_hyper()
                 check(lib.v2v_adam_step_dev(C.c_void_p(f.flat_param.data_ptr()), C.c_void_p(f.flat_grad.data_ptr()),

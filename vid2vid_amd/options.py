@@ -30,6 +30,9 @@ _DEFAULTS = dict(
     fix_update_fixed_params=False,   # True: update_fixed_params rebuilds the captured optimizer over all scales (the reference's
                                      # evident intent); False: the reference's observable behaviour (models/base_model.py docstring)
     compact_streams=False,    # multi-stream inference replays a plan with one row per ACTIVE stream (stream pool)
+    ema_decay=0.0,            # training: > 0 keeps an exponential moving average of the generator's weights inside the Adam step
+                              # and saves it as '<label>_net_G<s>_ema.pth' (DESIGN 3.17); 0 = off, nothing changes
+    use_ema=False,            # inference: load '<epoch>_net_G<s>_ema.pth' instead of '<epoch>_net_G<s>.pth'
 )
 
 

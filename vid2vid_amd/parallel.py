@@ -394,6 +394,8 @@ def sync_optimizers(optimizers, group=None, bucket_bytes=64 << 20, force_collect
         opt.grad_sync = gs
         opt.flat.ready = BucketReady(opt.flat, gs)   # in-backward bucket scheduling (counts start with the next forward pass)
         gs.broadcast(opt.flat.flat_param)
+        if getattr(opt, "ema_decay", 0.0) > 0.0:
+            gs.broadcast(opt.ema)                    # the averaged weights start equal too and then stay equal (optim.FusedAdam)
     _ACTIVE_SYNCS.append(gs)
     return gs
 
