@@ -858,6 +858,12 @@ int     v2v_onehot_conv7x7_norm(const void* labels, const void* inst, int32_t in
 int     v2v_onehot_conv7x7_batch(const void* labels, const void* inst, int32_t in_u8, const void* table, const float* bias,
                                  float* out, float* stats, int32_t N, int32_t T, int32_t H, int32_t W, int32_t label_nc,
                                  int32_t cout, int32_t cout_stride, int32_t dtype, int32_t slice, void* stream);
+/* 8 x 32 tiles one workgroup of the three entries above covers for these arguments: 1, or 2 (vertically stacked: each tap's
+ * weight blob is fetched once for both) where two tile rows exist and the launch keeps at least 1024 workgroups.  Outputs and
+ * statistics rows are the same bits either way.  The environment variable V2V_ONEHOT_PPT=1|2, read when a launch is built,
+ * forces either form (64-channel slices have the one-tile form only).  No launch; V2V_EINVAL for unsupported arguments. */
+int     v2v_onehot_conv_ppt(int32_t N, int32_t T, int32_t H, int32_t W, int32_t label_nc, int32_t has_inst,
+                            int32_t cout, int32_t dtype, int32_t slice);
 
 /* recordable device-to-device copy (rolling fake_B_prev window, vid2vid_model_G.py:228) */
 int v2v_memcpy_d2d(void* dst, const void* src, int64_t bytes, void* stream);

@@ -16,8 +16,10 @@
 // foreground mask and the window pack only (v2v_frame_prologue, csrc/pointwise.hip), with more scales the first pyramid
 // level comes straight from the maps (v2v_encode_labels_pooled); any other caller of v2v_encode_labels still gets the tensor.
 //
-// Workgroup = 256 threads = 8 x 32 output pixels x one SLICE of CS = 32 or 64 output channels (gridDim.y slices),
-// thread = pixel, CS fp32 accumulators in registers.  The packed table is [49 taps][slices][blob]: a blob is the slice's
+// Workgroup = 256 threads = PPT vertically stacked tiles of 8 x 32 output pixels x one SLICE of CS = 16, 32 or 64 output
+// channels (gridDim.y slices).  PPT = 1: thread = pixel, CS fp32 accumulators in registers.  PPT = 2 (launches of at least
+// 1024 such workgroups, onehot_pick_ppt; 16- and 32-channel slices): thread = the two pixels (py, px) and (py + 8, px), 2 x CS
+// accumulators, each tap's blob fetched once for both -- half the L2 -> LDS table traffic, the same bits.  The packed table is [49 taps][slices][blob]: a blob is the slice's
 // [T*per + 1][CS] weight rows (the extra row is zero: out-of-range labels and "no edge" point there, the inner loop has
 // no branches), each row PADDED by 16 bytes in global memory already, so that one tap's blob goes to LDS with plain
 // LDS-DMA (global_load_lds_dwordx4, no registers), double buffered, one barrier per tap, and lanes that read different
@@ -30,6 +32,7 @@
 // Epilogue: raw fp32 NHWC output (coalesced through LDS) + the per-tile (sum, sum^2) statistics row of the
 // training-mode norm that follows (fixed summation order, no atomics).
 #include "v2v_internal.h"
+#include <cstdlib>
 
 namespace v2v {
 
@@ -64,7 +67,9 @@ __device__ __forceinline__ unsigned lds_addr_of(const void* p) {
     return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p;
 }
 
-constexpr int OS_TH = 8, OS_TW = 32, OS_PH = OS_TH + 6, OS_PW = OS_TW + 6, OS_PHW = OS_PH * OS_PW;
+constexpr int OS_TH = 8, OS_TW = 32, OS_PW = OS_TW + 6;
+// halo entries per frame of a workgroup that covers `ppt` vertically stacked 8 x 32 tiles: (8 ppt + 6) x 38
+__host__ __device__ constexpr int os_phw(int ppt) { return (OS_TH * ppt + 6) * OS_PW; }
 constexpr size_t OS_EPI_LDS = (256 * 33 + 8 * 32 * 2 + 4) * sizeof(float);    // epilogue tile + partial sums + finalize flag
 
 __host__ __device__ constexpr int os_rowb(int cs, int es) { return cs * es + 16; }
@@ -72,17 +77,28 @@ __host__ __device__ inline int os_blob(int rows, int cs, int es) { return ((rows
 // LDS: [2 table blobs][row offsets][edge-row offsets] reused by the epilogue tile, then at `xoff` what must survive into the
 // epilogue: edge bits, k -> offset table, flag
 inline int os_ksteps(int T) { return (49 * T + 15) / 16; }
-inline size_t os_xoff(int T, int blob) {
-    size_t m = (size_t)2 * blob + (size_t)2 * T * OS_PHW * sizeof(unsigned short);
+inline size_t os_xoff(int T, int blob, int ppt) {
+    size_t m = (size_t)2 * blob + (size_t)2 * T * os_phw(ppt) * sizeof(unsigned short);
     if (m < OS_EPI_LDS) m = OS_EPI_LDS;
     return (m + 15) / 16 * 16;
 }
-inline size_t os_xbytes(int T, int ksteps) { return (size_t)((T * OS_PHW + 15) & ~15) + (size_t)ksteps * 32 + 16; }
+inline size_t os_xbytes(int T, int ksteps, int ppt) { return (size_t)((T * os_phw(ppt) + 15) & ~15) + (size_t)ksteps * 32 + 16; }
+// workgroups per CU the register budget is set for.  Two tiles: the LDS (35.0 KB of epilogue tile + the halo) admits 4 workgroups
+// per CU anyway, 3 with fp32 tables of 32 channels, so a budget of 128 / 168 VGPRs costs no occupancy
+__host__ __device__ constexpr int os_min_wg(int cs, int es, int ppt) {
+    return ppt == 1 ? (cs == 64 ? 4 : 6) : cs == 64 ? 2 : cs * es >= 128 ? 3 : 4;
+}
 inline size_t os_etab_bytes(int slices, int cs, int ksteps) { return (size_t)slices * ((cs + 31) / 32) * ksteps * 64 * 16; }
 
 // NT: frames per input (n_frames_G), 0 = run-time loop; BATCH = false is the one-sample kernel as it always was
-template <typename T, int CS, int NT, bool BATCH>
-__global__ __launch_bounds__(256, CS == 64 ? 4 : 6) void onehot_conv7x7_kernel(const OneHotConvArgs a) {
+// PPT: vertically stacked 8 x 32 tiles per workgroup = pixels per thread.  Thread (py, px) owns pixel (py + 8 h, px) of half h
+// with its own CS accumulators; the halo is (8 PPT + 6) x 38 offsets per frame, every tap's blob is fetched once and read for
+// all halves, and the epilogue runs once per half through the same LDS tile.  Per pixel the order of summation is that of
+// PPT = 1, each half writes the statistics row its 8 x 32 tile has at PPT = 1: every output bit is the same.  Table bytes per
+// output value are 1 / PPT of the one-tile kernel's.
+template <typename T, int CS, int NT, bool BATCH, int PPT = 1>
+__global__ __launch_bounds__(256, os_min_wg(CS, (int)sizeof(T), PPT)) void onehot_conv7x7_kernel(const OneHotConvArgs a) {
+    constexpr int OS_PHW = os_phw(PPT);
     constexpr int ES = (int)sizeof(T);
     constexpr int ROWB = os_rowb(CS, ES);
     constexpr int VPR = CS * ES / 16;                      // 16-byte vectors per row
@@ -97,13 +113,15 @@ __global__ __launch_bounds__(256, CS == 64 ? 4 : 6) void onehot_conv7x7_kernel(c
     const bool use_emfma = ES == 2 && a.etab != nullptr && a.inst != nullptr;
     unsigned char* const ebit_s = reinterpret_cast<unsigned char*>(smem + a.xoff);           // [T][PH][PW] 0 / 1 (kept through the epilogue)
     unsigned short* const koff_s = reinterpret_cast<unsigned short*>(smem + a.xoff + ((nT * OS_PHW + 15) & ~15));
-    int* const eflag = reinterpret_cast<int*>(koff_s + a.ksteps * 16);
-    bool any_e = false;
+    int* const eflag = reinterpret_cast<int*>(koff_s + a.ksteps * 16);    // [PPT]: an edge pixel in half h's tile + halo
+    bool any_e[PPT];
+#pragma unroll
+    for (int h = 0; h < PPT; ++h) any_e[h] = false;
 
     const int tid = threadIdx.x, wid = tid >> 6, lane = tid & 63;
     const int c0 = blockIdx.y * CS;                        // this workgroup's channel slice [c0, c0 + CS)
-    const int ty = blockIdx.x / a.tiles_w, tx = blockIdx.x - ty * a.tiles_w;
-    const int oh0 = ty * OS_TH, ow0 = tx * OS_TW;
+    const int ty = blockIdx.x / a.tiles_w, tx = blockIdx.x - ty * a.tiles_w;      // ty: row of PPT stacked tiles
+    const int oh0 = ty * (OS_TH * PPT), ow0 = tx * OS_TW;
     const int py = tid >> 5, px = tid & 31;
     const int H = a.H, W = a.W;
     const long long hw = (long long)H * W;
@@ -122,8 +140,10 @@ __global__ __launch_bounds__(256, CS == 64 ? 4 : 6) void onehot_conv7x7_kernel(c
         for (int p = wid; p < npieces; p += 4) os_glds16(src + p * 1024, d + p * 1024);
     };
     issue(0, tb0);
-    if (use_emfma && tid == 0) *eflag = 0;
+    if (use_emfma && tid < PPT) eflag[tid] = 0;
     __syncthreads();
+    // halves of this workgroup that exist: an odd number of tile rows leaves the last row of workgroups with one (uniform)
+    const int nh = PPT == 1 ? 1 : min(PPT, (H - oh0 + OS_TH - 1) / OS_TH);
 
     // ---- row offsets of the tile + halo, reflection applied (ReflectionPad2d(3) of the encoded tensor) ----
     for (int e = tid; e < nT * OS_PHW; e += 256) {
@@ -166,22 +186,30 @@ __global__ __launch_bounds__(256, CS == 64 ? 4 : 6) void onehot_conv7x7_kernel(c
         }
         off_s[e] = (unsigned short)((unsigned)lab < (unsigned)a.label_nc ? (unsigned)(t * a.per + lab) * ROWB : zero_off);
         eoff_s[e] = (unsigned short)(edge ? (unsigned)(t * a.per + a.label_nc) * ROWB : zero_off);
-        if (use_emfma) { ebit_s[e] = edge ? 1 : 0; any_e |= edge; }
+        if (use_emfma) {
+            ebit_s[e] = edge ? 1 : 0;
+#pragma unroll
+            for (int h = 0; h < PPT; ++h) any_e[h] |= edge && (PPT == 1 || (qy >= h * OS_TH && qy < h * OS_TH + OS_TH + 6));
+        }
     }
     if (use_emfma) {
         for (int k = tid; k < a.ksteps * 16; k += 256) {    // k = t * 49 + tap -> offset of edge bit (t, dy, dx) relative to a pixel's q0
             const int t = k / 49, tap = k - t * 49;
             koff_s[k] = (unsigned short)(t < nT ? t * OS_PHW + (tap / 7) * OS_PW + (tap % 7) : 0xffff);
         }
-        if (__builtin_amdgcn_ballot_w64(any_e) != 0 && lane == 0) *eflag = 1;     // benign race: every writer stores 1
+#pragma unroll
+        for (int h = 0; h < PPT; ++h)
+            if (__builtin_amdgcn_ballot_w64(any_e[h]) != 0 && lane == 0) eflag[h] = 1;     // benign race: every writer stores 1
     }
 
-    float acc[CS];
+    float accs[PPT][CS];
 #pragma unroll
-    for (int c = 0; c < CS; ++c) acc[c] = 0.f;
+    for (int h = 0; h < PPT; ++h)
+#pragma unroll
+        for (int c = 0; c < CS; ++c) accs[h][c] = 0.f;
     const unsigned sel_lo = a.sel_lo, sel_hi = a.sel_hi;
 
-    auto add_row = [&](const char* rowp) {
+    auto add_row = [&](float (&acc)[CS], const char* rowp) {
 #pragma unroll
         for (int j = 0; j < VPR; ++j) {
             const uint4 v = *reinterpret_cast<const uint4*>(rowp + j * 16);
@@ -204,29 +232,44 @@ __global__ __launch_bounds__(256, CS == 64 ? 4 : 6) void onehot_conv7x7_kernel(c
         char* const cur = (tap & 1) ? tb1 : tb0;
         if (tap + 1 < 49) issue(tap + 1, (tap & 1) ? tb0 : tb1);
         const int dy = tap / 7, dx = tap - dy * 7;
-        const int q = q0 + dy * OS_PW + dx;
+        const int qt = q0 + dy * OS_PW + dx;
         if constexpr (NT > 0) {
-            unsigned o[NT];
+            unsigned o[PPT][NT];
 #pragma unroll
-            for (int t = 0; t < NT; ++t) o[t] = off_s[t * OS_PHW + q];
+            for (int h = 0; h < PPT; ++h)
 #pragma unroll
-            for (int t = 0; t < NT; ++t) add_row(cur + o[t]);
+                for (int t = 0; t < NT; ++t) o[h][t] = off_s[t * OS_PHW + qt + h * (OS_TH * OS_PW)];
+#pragma unroll
+            for (int h = 0; h < PPT; ++h) {
+                // one half's row reads in flight at a time: hoisted above the other half's adds they do not fit the registers
+                if constexpr (PPT > 1) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int t = 0; t < NT; ++t) add_row(accs[h], cur + o[h][t]);
+            }
             if (a.inst && !use_emfma) {
-                unsigned e[NT];
-                bool any = false;
 #pragma unroll
-                for (int t = 0; t < NT; ++t) { e[t] = eoff_s[t * OS_PHW + q]; any |= e[t] != zero_off; }
-                if (__builtin_amdgcn_ballot_w64(any) != 0) {      // wave-uniform: most waves see no edge pixel at this tap
+                for (int h = 0; h < PPT; ++h) {
+                    const int q = qt + h * (OS_TH * OS_PW);
+                    unsigned e[NT];
+                    bool any = false;
 #pragma unroll
-                    for (int t = 0; t < NT; ++t) add_row(cur + e[t]);
+                    for (int t = 0; t < NT; ++t) { e[t] = eoff_s[t * OS_PHW + q]; any |= e[t] != zero_off; }
+                    if (__builtin_amdgcn_ballot_w64(any) != 0) {      // wave-uniform: most waves see no edge pixel at this tap
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) add_row(accs[h], cur + e[t]);
+                    }
                 }
             }
         } else {
-            for (int t = 0; t < nT; ++t) {
-                add_row(cur + off_s[t * OS_PHW + q]);
-                if (a.inst && !use_emfma) {
-                    const unsigned e = eoff_s[t * OS_PHW + q];
-                    if (__builtin_amdgcn_ballot_w64(e != zero_off) != 0) add_row(cur + e);
+#pragma unroll
+            for (int h = 0; h < PPT; ++h) {
+                const int q = qt + h * (OS_TH * OS_PW);
+                for (int t = 0; t < nT; ++t) {
+                    add_row(accs[h], cur + off_s[t * OS_PHW + q]);
+                    if (a.inst && !use_emfma) {
+                        const unsigned e = eoff_s[t * OS_PHW + q];
+                        if (__builtin_amdgcn_ballot_w64(e != zero_off) != 0) add_row(accs[h], cur + e);
+                    }
                 }
             }
         }
@@ -235,18 +278,30 @@ __global__ __launch_bounds__(256, CS == 64 ? 4 : 6) void onehot_conv7x7_kernel(c
     // ---- epilogue: bias, then 32-channel chunks through LDS: coalesced raw fp32 NHWC store + per-tile statistics ----
     if (a.bias) {
 #pragma unroll
-        for (int c = 0; c < CS; ++c) acc[c] += c0 + c < a.cout ? a.bias[c0 + c] : 0.f;
+        for (int c = 0; c < CS; ++c) {
+            const float b = c0 + c < a.cout ? a.bias[c0 + c] : 0.f;
+#pragma unroll
+            for (int h = 0; h < PPT; ++h) accs[h][c] += b;
+        }
     }
     __syncthreads();                                       // the table buffers are free
     float* const tile = reinterpret_cast<float*>(smem);    // [256 pixels][33]: stride 33 keeps the per-pixel writes conflict-free
     float* const red = tile + 256 * 33;                    // [8 parts][32][2]
-    const bool valid = oh0 + py < H && ow0 + px < W;
-    const bool ragged = oh0 + OS_TH > H || ow0 + OS_TW > W;
-    const bool do_emfma = use_emfma && *eflag != 0;        // no edge pixel in the tile + halo: nothing to add
     constexpr int NCH = (CS + 31) / 32, CW = CS < 32 ? CS : 32;       // 32-channel chunks of the slice; real channels per chunk (16-channel slices: 16)
     // (round 5 tried the tile in two halves of 128 pixels -- 26.8 KB of LDS per workgroup, 6 instead of 4 workgroups per CU: 6-13 % SLOWER on
     //  the 512x256 stems, profiles/r05_v16_ohab.txt: occupancy is not what this kernel lacks; and a third table buffer -- the blob of tap
     //  t + 2 in flight, counted vmcnt, raw s_barrier: 2-4 % slower, profiles/r05_v18_ohab.txt: nor is the blob's latency)
+    // rows of the statistics buffer: one per 8 x 32 tile, at PPT > 1 half h of tile-row pair ty is tile row PPT ty + h
+    const int stat_rows = PPT == 1 ? (int)gridDim.x : (H + OS_TH - 1) / OS_TH * a.tiles_w;
+#pragma unroll
+    for (int h = 0; h < PPT; ++h) {
+    if (h >= nh) break;                                    // (uniform) no such tile row: no loads, stores or statistics row
+    const float (&acc)[CS] = accs[h];
+    const int oh0h = oh0 + h * OS_TH;
+    const int stat_row = PPT == 1 ? (int)blockIdx.x : (ty * PPT + h) * a.tiles_w + tx;
+    const bool valid = oh0h + py < H && ow0 + px < W;
+    const bool ragged = oh0h + OS_TH > H || ow0 + OS_TW > W;
+    const bool do_emfma = use_emfma && eflag[h] != 0;      // no edge pixel in the tile + halo: nothing to add
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
 #pragma unroll
@@ -263,7 +318,7 @@ __global__ __launch_bounds__(256, CS == 64 ? 4 : 6) void onehot_conv7x7_kernel(c
                     for (int r = 0; r < 16; ++r) cm[m][r] = 0.f;
                 const int kg = lane >> 5;
                 const char* bsrc = a.etab + (((long long)blockIdx.y * NCH + k) * a.ksteps * 64 + lane) * 16;
-                const int qm0 = (2 * wid) * OS_PW + (lane & 31);
+                const int qm0 = (h * OS_TH + 2 * wid) * OS_PW + (lane & 31);
                 for (int ks = 0; ks < a.ksteps; ++ks) {
                     const bf16x8_t bfrag = *reinterpret_cast<const bf16x8_t*>(bsrc + (long long)ks * 64 * 16);
                     const uint4 ko = *reinterpret_cast<const uint4*>(koff_s + ks * 16 + kg * 8);
@@ -302,7 +357,7 @@ __global__ __launch_bounds__(256, CS == 64 ? 4 : 6) void onehot_conv7x7_kernel(c
         for (int it = 0; it < 8; ++it) {                   // 8 lanes x float4 = the 128 bytes of one pixel's chunk
             const int idx = it * 256 + tid;
             const int p = idx >> 3, c4 = (idx & 7) * 4;
-            const int oh = oh0 + (p >> 5), ow = ow0 + (p & 31);
+            const int oh = oh0h + (p >> 5), ow = ow0 + (p & 31);
             const int c = c0 + k * 32 + c4;
             if (oh < H && ow < W && c4 < CW && c < a.cout) {
                 float* op = out_b + ((long long)oh * W + ow) * a.cout_stride + c;
@@ -326,7 +381,7 @@ __global__ __launch_bounds__(256, CS == 64 ? 4 : 6) void onehot_conv7x7_kernel(c
             float t1 = 0.f, t2 = 0.f;
 #pragma unroll
             for (int part = 0; part < 8; ++part) { t1 += red[(part * 32 + tid) * 2]; t2 += red[(part * 32 + tid) * 2 + 1]; }
-            float* dst = a.stats + ((BATCH ? nb * gridDim.x + blockIdx.x : (long long)blockIdx.x) * a.cout + c0 + k * 32 + tid) * 2;
+            float* dst = a.stats + ((BATCH ? nb * stat_rows + stat_row : (long long)stat_row) * a.cout + c0 + k * 32 + tid) * 2;
             if (a.fin_counter != nullptr) {          // read back by the finalizing workgroup: agent-scope write-through store
                 const unsigned long long bits = (unsigned long long)__float_as_uint(t1) | ((unsigned long long)__float_as_uint(t2) << 32);
                 __hip_atomic_store(reinterpret_cast<unsigned long long*>(dst), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -335,6 +390,7 @@ __global__ __launch_bounds__(256, CS == 64 ? 4 : 6) void onehot_conv7x7_kernel(c
                 dst[1] = t2;
             }
         }
+    }
     }
     if (a.stats == nullptr || a.fin_counter == nullptr) return;
     // ---- norm finalize by the LAST workgroup of this channel slice (get_norm_layer, models/networks.py:23-30): replaces a
@@ -356,7 +412,7 @@ __global__ __launch_bounds__(256, CS == 64 ? 4 : 6) void onehot_conv7x7_kernel(c
         const int c = tid % CS, ph = tid / CS;
         const int ncol = c0 + c;
         double s1 = 0.0, s2 = 0.0;
-        if (ncol < a.cout) sum_stat_rows<16>(a.stats, (long long)ncol * 2, (long long)a.cout * 2, ph, PH, (int)gridDim.x, s1, s2);
+        if (ncol < a.cout) sum_stat_rows<16>(a.stats, (long long)ncol * 2, (long long)a.cout * 2, ph, PH, stat_rows, s1, s2);
         acc2[(ph * CS + c) * 2 + 0] = s1;
         acc2[(ph * CS + c) * 2 + 1] = s2;
         __syncthreads();
@@ -383,10 +439,16 @@ __global__ __launch_bounds__(256, CS == 64 ? 4 : 6) void onehot_conv7x7_kernel(c
 
 struct OneHotConvOp : Op {
     OneHotConvArgs a; int dtype, cs, slices, tiles; int N = 1;
-    template <typename T, int CS, int NT> int go(hipStream_t s) { return N > 1 ? go_b<T, CS, NT, true>(s) : go_b<T, CS, NT, false>(s); }
-    template <typename T, int CS, int NT, bool BATCH> int go_b(hipStream_t s) {
-        const size_t lds = (size_t)a.xoff + os_xbytes(a.T, a.ksteps);
-        auto kern = onehot_conv7x7_kernel<T, CS, NT, BATCH>;
+    int ppt = 1;                                           // stacked tiles per workgroup; `tiles` is the grid: workgroups per slice
+    template <typename T, int CS, int NT> int go(hipStream_t s) {
+        if constexpr (CS != 64) {                          // (onehot_ppt2_built)
+            if (ppt == 2) return N > 1 ? go_b<T, CS, NT, true, 2>(s) : go_b<T, CS, NT, false, 2>(s);
+        }
+        return N > 1 ? go_b<T, CS, NT, true, 1>(s) : go_b<T, CS, NT, false, 1>(s);
+    }
+    template <typename T, int CS, int NT, bool BATCH, int PPT> int go_b(hipStream_t s) {
+        const size_t lds = (size_t)a.xoff + os_xbytes(a.T, a.ksteps, PPT);
+        auto kern = onehot_conv7x7_kernel<T, CS, NT, BATCH, PPT>;
         static bool attr_done = false;
         if (!attr_done) {
             hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -513,6 +575,25 @@ static int slice_of(int cout, int dtype, int slice) {
     (void)dtype;
     return slice == 64 ? 64 : (slice == 0 && cout <= 16) ? 16 : 32;
 }
+// Tiles per workgroup (the kernel's PPT).  Two stacked tiles halve the table bytes a launch streams from L2 to LDS, and halve
+// its workgroups: the pair form is taken when there are two tile rows to pair and the launch still has OS_PPT2_MIN_WG
+// workgroups = 4 per CU, the number the LDS admits.  Measured alone, bf16, cold (profiles/onehot_ppt_bench.json): 108 -> 128
+// @512x256, 1024 pair workgroups, 169 -> 157 us; with 576 (108 -> 128 @384x192) 117 -> 124 us, with 512 (108 -> 64 @512x256)
+// 93 -> 100 us, with 256 65 -> 78 us: below four per CU the chip is short of waves and the pair form loses.
+// V2V_ONEHOT_PPT=1|2, read when the op is built, forces either form.
+constexpr long long OS_PPT2_MIN_WG = 1024;
+static bool onehot_ppt2_built(int cs) { return cs != 64; }       // 64-channel slices stay on one tile: 2 x 64 accumulators, DESIGN 3
+static size_t onehot_lds(int T, int blob, int ppt) { return os_xoff(T, blob, ppt) + os_xbytes(T, os_ksteps(T), ppt); }
+static bool onehot_fits(int T, int blob, int ppt) {
+    return onehot_lds(T, blob, ppt) <= 156 * 1024 && (size_t)T * os_phw(ppt) + 49 * OS_PW <= 65535;
+}
+static int onehot_pick_ppt(int N, int T, int H, int W, int cs, int slices, int blob) {
+    if (!onehot_ppt2_built(cs) || !onehot_fits(T, blob, 2)) return 1;
+    const char* env = getenv("V2V_ONEHOT_PPT");
+    if (env && (env[0] == '1' || env[0] == '2') && env[1] == 0) return env[0] - '0';
+    const long long th = ceil_div(H, OS_TH), tw = ceil_div(W, OS_TW);
+    return th >= 2 && ceil_div(th, 2) * tw * slices * N >= OS_PPT2_MIN_WG ? 2 : 1;
+}
 static bool onehot_args_ok(int cin, int cout, int dtype, int slice) {
     return cin >= 1 && cout >= 1 && cout <= 128 && (dtype == V2V_F32 || dtype == V2V_BF16) && (slice == 0 || slice == 32 || slice == 64);
 }
@@ -563,6 +644,15 @@ extern "C" int v2v_onehot_conv_stats_rows(int32_t H, int32_t W) {
     return (int)(ceil_div(H, OS_TH) * ceil_div(W, OS_TW));
 }
 
+extern "C" int v2v_onehot_conv_ppt(int32_t N, int32_t T, int32_t H, int32_t W, int32_t label_nc, int32_t has_inst,
+                                   int32_t cout, int32_t dtype, int32_t slice) {
+    if (N < 1 || T < 1 || H < 4 || W < 4 || label_nc < 1 || !onehot_args_ok(1, cout, dtype, slice)) return V2V_EINVAL;
+    const int cs = slice_of(cout, dtype, slice), es = dtype == V2V_BF16 ? 2 : 4;
+    const int blob = os_blob(T * (label_nc + (has_inst ? 1 : 0)), cs, es);
+    if (!onehot_fits(T, blob, 1)) return V2V_EINVAL;
+    return onehot_pick_ppt(N, T, H, W, cs, (int)ceil_div(cout, cs), blob);
+}
+
 static int onehot_conv_submit(const void* labels, const void* inst, int32_t in_u8, const void* table, const float* bias,
                               float* out, float* stats, int32_t T, int32_t H, int32_t W, int32_t label_nc,
                               int32_t cout, int32_t cout_stride, int32_t dtype, int32_t slice, const v2v_onehot_norm* fin, void* stream,
@@ -580,16 +670,17 @@ static int onehot_conv_submit(const void* labels, const void* inst, int32_t in_u
     const int rows = T * per;
     const int blob = os_blob(rows, cs, es);
     const int ksteps = os_ksteps(T);
-    const size_t lds = os_xoff(T, blob) + os_xbytes(T, ksteps);
-    if ((rows + 1) * os_rowb(cs, es) > 65535 || lds > 156 * 1024 || (size_t)T * OS_PHW + 49 * OS_PW > 65535) {
+    if ((rows + 1) * os_rowb(cs, es) > 65535 || !onehot_fits(T, blob, 1)) {
         set_error("onehot_conv7x7: T * (label_nc + 1) = %d weight rows do not fit the LDS", rows); return V2V_EINVAL;
     }
+    const int slices = (int)ceil_div(cout, cs);
+    const int ppt = onehot_pick_ppt(N, T, H, W, cs, slices, blob);
     auto op = std::make_unique<OneHotConvOp>();
     op->a = OneHotConvArgs{labels, inst, reinterpret_cast<const char*>(table), bias, out, stats, T, H, W, label_nc, per, cout, cout_stride,
                            (int)ceil_div(W, OS_TW), in_u8, blob, 0x00003f80u, 0x3f800000u,
                            (inst && has_edge_tab(rows, dtype, T, label_nc))
                                ? reinterpret_cast<const char*>(table) + 49ll * ceil_div(cout, cs) * blob : nullptr,
-                           ksteps, (int)os_xoff(T, blob),
+                           ksteps, (int)os_xoff(T, blob, ppt),
                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0.0, 0.0};
     if (fin != nullptr) {
         if (!stats || !fin->counter || !fin->scale_shift || fin->count <= 0) {
@@ -601,8 +692,8 @@ static int onehot_conv_submit(const void* labels, const void* inst, int32_t in_u
         a.fin_inv_count = 1.0 / (double)fin->count;
         a.fin_unbias = fin->count > 1 ? (double)fin->count / (double)(fin->count - 1) : 1.0;
     }
-    op->dtype = dtype; op->cs = cs; op->slices = (int)ceil_div(cout, cs); op->N = N;
-    op->tiles = (int)(ceil_div(H, OS_TH) * ceil_div(W, OS_TW));
+    op->dtype = dtype; op->cs = cs; op->slices = slices; op->N = N; op->ppt = ppt;
+    op->tiles = (int)(ceil_div(ceil_div(H, OS_TH), ppt) * ceil_div(W, OS_TW));
     return submit(std::move(op), stream);
 }
 
