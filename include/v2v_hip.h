@@ -803,6 +803,20 @@ int       v2v_plan_lane_wait(int32_t waiter, int32_t signal);
  * x*255, clipped, truncated) or uint8 [H][W][3] (tensor2label: argmax over C > 1 planes or the stored id for C == 1,
  * coloured through cmap[n_label][3]).  Integer-exact against the reference's numpy arithmetic. */
 int v2v_tensor2im(const float* x, uint8_t* out, int32_t C, int32_t H, int32_t W, int32_t normalize, void* stream);
+/* v2v_tensor2im for the K dense rows of a frame plan's output in ONE launch, delivered as S images: frames is planar
+ * fp32 [K][C][H][W], out uint8 [S][H][W][C].  mode[K] and row_slot[K] are int32 in device memory, read when the launch runs (the
+ * words a slot or pool plan refreshes per replay); either may be NULL: without row_slot row k is image k (K == S required),
+ * without mode every row is in mode 0.
+ *   image s = v2v_tensor2im of the first row k with row_slot[k] == s and mode[k] 0 or 1, bit for bit (the same fp32 operations
+ *             in the same order, clamp to [0, 255] with NaN -> 0, truncating cast);
+ *   image s = all zero bytes where no such row exists: an idle slot, a slot no row names, a row of mode 2 (or any other value).
+ * A row whose slot word is outside [0, S) writes nothing; a row of mode 2 is not read, so NaN in it reaches nothing.  EVERY byte
+ * of out is written by the launch: nothing has to clear it first.  Where H W is a multiple of 4, frames is 16-byte and out 4-byte
+ * aligned, a thread converts 4 pixels from one 16-byte load per plane into C packed 4-byte words; otherwise one byte per thread;
+ * both give the same bytes.  V2V_EINVAL for frames or out NULL, K < 1, S < K, S > 65535, C outside 1..4, H or W < 1, row_slot ==
+ * NULL with K != S, out overlapping frames.  Recorded into a plan as op "frames_u8". */
+int v2v_frames_u8(const float* frames, uint8_t* out, const int32_t* mode, const int32_t* row_slot, int32_t K, int32_t S,
+                  int32_t C, int32_t H, int32_t W, int32_t normalize, void* stream);
 /* tensor2flow (util/util.py:89-107): flow planar fp32 [2][H][W] -> uint8 [H][W][3], hue = direction / 2 degrees, value = magnitude
  * min-max normalised over the image, full saturation, HSV -> RGB as OpenCV's 8-bit conversion.  range_ws: 2 uint32 of scratch. */
 int v2v_tensor2flow(const float* flow, uint8_t* out, uint32_t* range_ws, int32_t H, int32_t W, void* stream);

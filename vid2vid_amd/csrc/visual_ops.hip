@@ -31,6 +31,80 @@ __global__ __launch_bounds__(256) void tensor2im_kernel(const Im2Args a) {
     }
 }
 
+// Frames of a multi-stream frame plan as uint8 images (v2v_frames_u8): tensor2im for K dense rows in one launch,
+// delivered into S images under the plan's per-row words.  Image s (blockIdx.y) is made from the first row k with row_slot[k] == s
+// (row s without row_slot) whose mode is 0 or 1; an image without such a row is written as zeros.  The words are uniform over the
+// workgroup: every thread scans the K of them once.
+struct FramesU8Args {
+    const float* x; unsigned char* out; const int* mode; const int* row_slot;
+    long long hw; int K, S, C, normalize;
+};
+
+// the arithmetic of tensor2im_kernel, operation for operation
+__device__ __forceinline__ unsigned frames_u8_byte(float x, int normalize) {
+    float v = normalize ? ((x + 1.f) / 2.f) * 255.f : x * 255.f;
+    v = fminf(fmaxf(v, 0.f), 255.f);
+    return (unsigned)(unsigned char)(int)v;
+}
+
+__device__ __forceinline__ int frames_u8_row(const FramesU8Args& a, int s) {
+    for (int k = 0; k < a.K; ++k) {
+        if ((a.row_slot ? a.row_slot[k] : k) != s) continue;
+        const int m = a.mode ? a.mode[k] : 0;
+        if (m == 0 || m == 1) return k;
+    }
+    return -1;
+}
+
+// Wide path (H W a multiple of 4, planes 16-byte aligned, images 4-byte aligned): a thread converts 4 consecutive pixels, one
+// 16-byte load per plane, and stores their 4 CC interleaved bytes as CC packed words.
+template <int CC>
+__global__ __launch_bounds__(256) void frames_u8_wide_kernel(const FramesU8Args a) {
+    const int s = blockIdx.y;
+    const int row = frames_u8_row(a, s);
+    const long long nvec = a.hw >> 2;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    unsigned* const out = reinterpret_cast<unsigned*>(a.out + (long long)s * a.hw * CC);
+    const float* const x = a.x + (long long)(row < 0 ? 0 : row) * CC * a.hw;
+    for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += stride) {
+        unsigned w[CC];
+#pragma unroll
+        for (int j = 0; j < CC; ++j) w[j] = 0u;
+        if (row >= 0) {
+#pragma unroll
+            for (int c = 0; c < CC; ++c) {
+                const f32x4 p = *reinterpret_cast<const f32x4*>(x + (long long)c * a.hw + 4 * v);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int byte = i * CC + c;             // position among the 4 CC bytes of this thread
+                    w[byte >> 2] |= frames_u8_byte(p[i], a.normalize) << (8 * (byte & 3));
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < CC; ++j) out[v * CC + j] = w[j];
+    }
+}
+
+// Scalar path: any H W and any alignment, one byte per thread and trip, the loop of tensor2im_kernel per image.
+__global__ __launch_bounds__(256) void frames_u8_scalar_kernel(const FramesU8Args a) {
+    const int s = blockIdx.y;
+    const int row = frames_u8_row(a, s);
+    const long long total = a.hw * a.C;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    unsigned char* const out = a.out + (long long)s * total;
+    const float* const x = a.x + (long long)(row < 0 ? 0 : row) * total;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        unsigned char b = 0;
+        if (row >= 0) {
+            const long long pix = e / a.C;
+            const int c = (int)(e - pix * a.C);
+            b = (unsigned char)frames_u8_byte(x[(long long)c * a.hw + pix], a.normalize);
+        }
+        out[e] = b;
+    }
+}
+
 struct Lab2Args { const float* x; unsigned char* out; const unsigned char* cmap; int C, H, W, n; };
 
 // label = C > 1 ? argmax_c x[c] (first maximum, torch.max) : the stored value; out[h][w][:] = cmap[label] (0 beyond n)
@@ -131,6 +205,26 @@ struct Im2Op : Op {
     }
     const char* name() const override { return "tensor2im"; }
 };
+struct FramesU8Op : Op {
+    FramesU8Args a;
+    bool wide;
+    int launch(hipStream_t s) override {
+        const dim3 b(256);
+        if (wide) {
+            const dim3 g(grid_for(a.hw >> 2, 256, 1024), (unsigned)a.S);
+            switch (a.C) {
+                case 1: hipLaunchKernelGGL(frames_u8_wide_kernel<1>, g, b, 0, s, a); break;
+                case 2: hipLaunchKernelGGL(frames_u8_wide_kernel<2>, g, b, 0, s, a); break;
+                case 3: hipLaunchKernelGGL(frames_u8_wide_kernel<3>, g, b, 0, s, a); break;
+                default: hipLaunchKernelGGL(frames_u8_wide_kernel<4>, g, b, 0, s, a); break;
+            }
+        } else {
+            hipLaunchKernelGGL(frames_u8_scalar_kernel, dim3(grid_for(a.hw * a.C, 256, 1024), (unsigned)a.S), b, 0, s, a);
+        }
+        return check_launch();
+    }
+    const char* name() const override { return "frames_u8"; }
+};
 struct Lab2Op : Op {
     Lab2Args a;
     int launch(hipStream_t s) override {
@@ -148,6 +242,22 @@ extern "C" int v2v_tensor2im(const float* x, uint8_t* out, int32_t C, int32_t H,
     if (!x || !out || C < 1 || C > 3 || H < 1 || W < 1) { set_error("tensor2im: bad argument (1..3 planes)"); return V2V_EINVAL; }
     auto op = std::make_unique<Im2Op>();
     op->a = Im2Args{x, out, C, H, W, normalize};
+    return submit(std::move(op), stream);
+}
+
+extern "C" int v2v_frames_u8(const float* frames, uint8_t* out, const int32_t* mode, const int32_t* row_slot, int32_t K, int32_t S,
+                             int32_t C, int32_t H, int32_t W, int32_t normalize, void* stream) {
+    if (!frames || !out || K < 1 || S < K || S > 65535 || C < 1 || C > 4 || H < 1 || W < 1) {
+        set_error("frames_u8: bad argument (1 <= K <= S <= 65535 rows / images, 1..4 planes)"); return V2V_EINVAL;
+    }
+    if (!row_slot && K != S) { set_error("frames_u8: without row_slot row k is image k: K == S"); return V2V_EINVAL; }
+    const long long hw = (long long)H * W;
+    const unsigned char* const fb = reinterpret_cast<const unsigned char*>(frames);
+    if (fb + 4 * hw * C * K > out && fb < out + hw * C * S) { set_error("frames_u8: out must not overlap frames"); return V2V_EINVAL; }
+    auto op = std::make_unique<FramesU8Op>();
+    op->a = FramesU8Args{frames, out, mode, row_slot, hw, K, S, C, normalize};
+    // every plane starts 16-byte aligned and every image 4-byte aligned exactly when the bases are and H W is whole vectors
+    op->wide = hw % 4 == 0 && reinterpret_cast<uintptr_t>(frames) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0;
     return submit(std::move(op), stream);
 }
 

@@ -2160,6 +2160,27 @@ class Engine:
               "window_scatter_pool")
         self.label("window_scatter")
 
+    def frames_u8(self, frames, mode=None, row_slot=None, S=None, normalize=True):
+        """uint8 images (S, H, W, C) of the fp32 planar rows `frames` (K, C, H, W) in one launch (v2v_frames_u8): image
+        s is tensor2im of the row k with row_slot[k] == s (row s without row_slot; S = K then) whose mode[k] is 0 or 1, and all
+        zero bytes where there is none.  mode / row_slot: int32 (K,) device tensors read when the launch runs, or None.  The
+        launch writes every byte of the image buffer it returns."""
+        K, Cc, H, W = frames.shape
+        S = K if S is None else int(S)
+        if frames.dtype != torch.float32 or not frames.is_contiguous():
+            raise ValueError("frames_u8: contiguous fp32 frames (K, C, H, W)")
+        for t in (mode, row_slot):
+            if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (K,) or not t.is_contiguous()):
+                raise ValueError("frames_u8: mode and row_slot are int32 (K,)")
+            if t is not None:
+                self._keep(t)
+        out = torch.empty((S, H, W, Cc), dtype=torch.uint8, device=self.device)
+        self._keep(out)
+        check(lib.v2v_frames_u8(_ptr(frames), _ptr(out), _ptr(mode), _ptr(row_slot), K, S, Cc, H, W, int(bool(normalize)),
+                                _stream()), "frames_u8")
+        self.label("frames_u8")
+        return out
+
     def resample_flow(self, img, flow):
         N, Cc, H, W = img.shape
         if self._training() and (img.requires_grad or flow.requires_grad):

@@ -73,13 +73,17 @@ class _FramePlan:
     of the tail runs for all B streams whatever their mode.
     pool (a _StreamPool): the plan has B = K dense rows and serves K of the pool's S slots: `prev` IS the pool's
     windows, row k works on slot row_slot[k] under row_mode[k] (0 steady, 1 raw-only first frame; int32 (K,), refreshed per call
-    like slot_mode).  K == 1 emits the batch-1 body, K > 1 the per-stream one; only the head and the tail know about slots."""
+    like slot_mode).  K == 1 emits the batch-1 body, K > 1 the per-stream one; only the head and the tail know about slots.
+    frames_u8: the plan's last launch converts its fake_B rows into `out["image"]`, uint8 (B, H, W, 3) -- (S, H, W, 3)
+    for a pool plan -- under the plan's own slot_mode / row_slot words: idle streams and slots come out as zero bytes."""
 
-    def __init__(self, model, H, W, in_ch, has_inst, use_raw_only, use_graph=True, u8=False, B=1, slots=False, pool=None):
+    def __init__(self, model, H, W, in_ch, has_inst, use_raw_only, use_graph=True, u8=False, B=1, slots=False, pool=None,
+                 frames_u8=False):
         opt, eng = model.opt, model.engine
         self.model, self.eng = model, eng
         self.H, self.W, self.use_raw_only, self.B = H, W, use_raw_only, B
         self.slots = bool(slots)
+        self.frames_u8 = bool(frames_u8)
         if self.slots and (B < 2 or use_raw_only):
             raise ValueError("a slot plan has B > 1 streams and decides raw-only frames per stream (slot_mode 1)")
         self.pool = pool
@@ -315,6 +319,7 @@ class _FramePlan:
             last = Act(x0.t[..., (tG - 1) * per:], per)
             last = eng.unpack(last)
             self.out["real_A_last"] = last[0] if B == 1 else last
+        self._emit_image()
         self.conv_log = list(eng.conv_log)
 
     def _real_A_last(self):
@@ -358,7 +363,21 @@ class _FramePlan:
                 eng.window_scatter(self.prev[0], prev, self.row_slot)
         self.out["flow0"], self.out["weight0"], self.out["raw0"] = flow, weight, raw
         self.out["fake_B"] = fake_B
+        self._emit_image()
         self.conv_log = list(eng.conv_log)
+
+    def _emit_image(self):
+        """frames_u8 plans: the uint8 images of this replay's fake_B rows as the plan's last launch, on the lane that produced them
+        (lane 0).  It reads the fake_B buffer whichever launch wrote it, and decides idle rows / slots itself from the plan's words:
+        a slot plan's idle rows come out zero also where no blend launch zeroed them, a pool plan's K rows land in its S images."""
+        if not self.frames_u8:
+            return
+        fake_B = self.out["fake_B"]
+        fake_B = fake_B.view(self.B, -1, self.H, self.W)
+        if self.pool is not None:
+            self.out["image"] = self.eng.frames_u8(fake_B, self.slot_mode, self.row_slot, S=self.pool.S)
+        else:
+            self.out["image"] = self.eng.frames_u8(fake_B, self.slot_mode if self.slots else None)
 
     def _gathered(self, si):
         """Pool plans off the rolling blend: the windows of this plan's rows at scale si as a dense (K, tG-1, 3, h, w) copy, by
@@ -500,10 +519,11 @@ class Vid2VidModelG(BaseModel):
                         views[p].copy_(saved[name])
 
     # ------------------------------------------------------------------ inference
-    def _frame_plan(self, H, W, in_ch, has_inst, use_raw_only, u8=False, B=1, slots=False, pool=None):
-        """pool: the slot capacity S of a pool plan with B rows; its key ends in ("pool", S)."""
+    def _frame_plan(self, H, W, in_ch, has_inst, use_raw_only, u8=False, B=1, slots=False, pool=None, frames_u8=False):
+        """pool: the slot capacity S of a pool plan with B rows; its key ends in ("pool", S).
+        frames_u8: the plan ends in the uint8 image launch; only then its key gains a last field "frames_u8"."""
         key = (H, W, in_ch, has_inst, use_raw_only, self.precision, u8, B) + (("slots",) if slots else ()) + \
-              ((("pool", pool),) if pool else ())
+              ((("pool", pool),) if pool else ()) + (("frames_u8",) if frames_u8 else ())
         fp = self._plans.get(key)
         if fp is None:
             self.engine.refresh_weights()
@@ -511,7 +531,8 @@ class Vid2VidModelG(BaseModel):
             # building a plan replays it (warm-up, tile search): the live windows are put back behind that
             saved = [w.clone() for w in windows.windows] if pool else []
             fp = _FramePlan(self, H, W, in_ch, has_inst, use_raw_only,
-                            use_graph=getattr(self.opt, "use_graph", True), u8=u8, B=B, slots=slots, pool=windows)
+                            use_graph=getattr(self.opt, "use_graph", True), u8=u8, B=B, slots=slots, pool=windows,
+                            frames_u8=frames_u8)
             for w, keep in zip(windows.windows if pool else [], saved):
                 w.copy_(keep)
             self._plans[key] = fp
@@ -529,14 +550,14 @@ class Vid2VidModelG(BaseModel):
         `counts` (default 1..S) ahead of time: each plan records, and searches its tiles, when it is first built -- here rather
         than in the first call that happens to have that many live clips.  in_ch, has_inst, u8: as the calls will have them
         (channels of input_A, whether inst_A is given and used, uint8 label maps).  Activations cost one stream-size per row of
-        every plan built: S (S + 1) / 2 stream-sizes for all counts."""
+        every plan built: S (S + 1) / 2 stream-sizes for all counts.  The plans are built for opt.frames_u8 as it is now."""
         counts = list(range(1, S + 1)) if counts is None else sorted(set(int(k) for k in counts))
         if S < 2 or not counts or counts[0] < 1 or counts[-1] > S:
             raise ValueError("prepare_streams: S >= 2 slots and active counts within 1..S")
         with torch.no_grad():
             for K in counts:
                 self._frame_plan(H, W, in_ch, bool(has_inst and self.opt.use_instance and self.opt.label_nc != 0), False, bool(u8),
-                                 B=K, pool=S)
+                                 B=K, pool=S, frames_u8=bool(getattr(self.opt, "frames_u8", False)))
 
     @staticmethod
     def _slot_set(arg, B, name):
@@ -579,7 +600,12 @@ class Vid2VidModelG(BaseModel):
         opt.compact_streams (read per call): with B > 1 the call replays a plan with one row per active stream, on
         windows the model owns; the contract above is unchanged.  Setting it while sequences run outside a pool is a ValueError
         (assign fake_B_prev = None with it); clearing it while sequences run continues them, the pool's windows being copied
-        once into the slot or plain plan's own."""
+        once into the slot or plain plan's own.
+        opt.frames_u8 (read per call): the first result is `image`, torch.uint8 (B,H,W,output_nc) for every B, instead
+        of fake_B: image[b] == visual.tensor2im(fake_B[b]) for every active stream b, fake_B being what the same call returns with
+        the option off, and an idle stream's image is all ZERO bytes (not the 127 that zero planes convert to).  The images are
+        written by the last launch of the frame plan; real_A_last, fake_B_prev and every other state are as with the option off,
+        and the option may change between the calls of running sequences."""
         opt = self.opt
         tG = opt.n_frames_G
         with torch.no_grad():
@@ -604,12 +630,14 @@ class Vid2VidModelG(BaseModel):
                     raise ValueError("inference: %d sequence(s) given while %d are running; assign fake_B_prev = None to restart"
                                      % (B, running))
             has_inst = bool(opt.use_instance and inst_A is not None and opt.label_nc != 0)
+            img = bool(getattr(opt, "frames_u8", False))
             if slot_call and B == 1:
                 # one stream needs no slot plan: idle is no call at all, a restart is fake_B_prev = None
                 if not act[0]:
                     last_C = in_ch if opt.label_nc == 0 else opt.label_nc + int(has_inst)
-                    return (torch.zeros(1, opt.output_nc, H, W, dtype=torch.float32, device=self.device),
-                            torch.zeros(last_C, H, W, dtype=torch.float32, device=self.device))
+                    idle = torch.zeros(1, H, W, opt.output_nc, dtype=torch.uint8, device=self.device) if img else \
+                        torch.zeros(1, opt.output_nc, H, W, dtype=torch.float32, device=self.device)
+                    return idle, torch.zeros(last_C, H, W, dtype=torch.float32, device=self.device)
                 if rst[0]:
                     self.fake_B_prev = None
                     self.is_first_frame = True
@@ -622,13 +650,13 @@ class Vid2VidModelG(BaseModel):
             if B > 1 and getattr(opt, "compact_streams", False):
                 if not slot_call:
                     act, rst = [True] * B, [False] * B
-                return self._inference_pool(input_A, input_B, inst_A, act, rst, has_inst, u8)
+                return self._inference_pool(input_A, input_B, inst_A, act, rst, has_inst, u8, img)
             if self._slots_on:
                 if not slot_call:
                     act, rst = [True] * B, [False] * B
-                return self._inference_slots(input_A, input_B, inst_A, act, rst, has_inst, u8)
+                return self._inference_slots(input_A, input_B, inst_A, act, rst, has_inst, u8, img)
             use_raw_only = bool(opt.no_first_img and self.is_first_frame)
-            fp = self._frame_plan(H, W, in_ch, has_inst, use_raw_only, u8, B)
+            fp = self._frame_plan(H, W, in_ch, has_inst, use_raw_only, u8, B, frames_u8=img)
             dev = self.device
             # ---- stage inputs (H2D or D2D) into the plan's static buffers; pinned host tensors copy asynchronously ----
             if fp.label_mode:
@@ -649,15 +677,16 @@ class Vid2VidModelG(BaseModel):
             fp.run()
             # fresh tensors per frame, as the reference returns them (the plan's output buffers are overwritten by the
             # next replay; a caller collecting a clip must not see every entry alias the last frame)
-            return fp.out["fake_B"].clone(), fp.out["real_A_last"].clone()
+            return fp.out["image" if img else "fake_B"].clone(), fp.out["real_A_last"].clone()
 
-    def _inference_slots(self, input_A, input_B, inst_A, act, rst, has_inst, u8):
+    def _inference_slots(self, input_A, input_B, inst_A, act, rst, has_inst, u8, img=False):
         """One replay of the slot plan (B > 1).  act / rst: B bools.  On the first frame of the model
-        (fake_B_prev = None) every active stream starts a sequence and the windows of the idle ones are zero."""
+        (fake_B_prev = None) every active stream starts a sequence and the windows of the idle ones are zero.
+        img (opt.frames_u8): the uint8 images the plan's last launch wrote, idle rows zero, instead of fake_B."""
         opt, dev = self.opt, self.device
         tG = opt.n_frames_G
         B, _, in_ch, H, W = input_A.shape
-        fp = self._frame_plan(H, W, in_ch, has_inst, False, u8, B, slots=True)
+        fp = self._frame_plan(H, W, in_ch, has_inst, False, u8, B, slots=True, frames_u8=img)
         if self.is_first_frame:
             rst = list(act)
         # ---- stage the rows of the active streams; an idle stream's rows are not read (the buffers keep its last valid rows) ----
@@ -690,21 +719,28 @@ class Vid2VidModelG(BaseModel):
         self._active_plan = fp
         self.fake_B_prev = fp.prev
         fp.run()
+        if img:                  # the image launch zeroed the idle rows itself, with or without a blend launch in front of it
+            return fp.out["image"].clone(), fp.out["real_A_last"].clone()
         fake = fp.out["fake_B"].clone()
         if not fp.blend_launch and len(rows) != B:        # no blend launch in this generator: nothing wrote the idle rows' zeros
             fake[[b for b in range(B) if not act[b]]] = 0
         return fake, fp.out["real_A_last"].clone()
 
-    def _inference_pool(self, input_A, input_B, inst_A, act, rst, has_inst, u8):
+    def _inference_pool(self, input_A, input_B, inst_A, act, rst, has_inst, u8, img=False):
         """One call of a compacting model (opt.compact_streams, B = S > 1 slots): the contract of _inference_slots,
-        by a replay of the pool plan that has one row per ACTIVE stream -- row k runs slot rows[k], rows ascending."""
+        by a replay of the pool plan that has one row per ACTIVE stream -- row k runs slot rows[k], rows ascending.
+        img (opt.frames_u8): the plan's last launch delivers the (S,H,W,3) uint8 images, idle slots zero; no zero tensor and no
+        indexed copy for the frames."""
         opt, dev = self.opt, self.device
         tG = opt.n_frames_G
         S, _, in_ch, H, W = input_A.shape
         rows = [b for b in range(S) if act[b]]
         K = len(rows)
         last_C = in_ch if opt.label_nc == 0 else opt.label_nc + int(has_inst)
-        fake = torch.zeros(S, opt.output_nc, H, W, dtype=torch.float32, device=dev)
+        if not img:
+            fake = torch.zeros(S, opt.output_nc, H, W, dtype=torch.float32, device=dev)
+        elif K == 0:
+            fake = torch.zeros(S, H, W, opt.output_nc, dtype=torch.uint8, device=dev)
         real_A_last = torch.zeros(S, last_C, H, W, dtype=torch.float32, device=dev)
         if K == 0:                      # nothing is live: no replay, no state touched
             return fake, real_A_last
@@ -712,7 +748,7 @@ class Vid2VidModelG(BaseModel):
         if not self.is_first_frame and (self._active_plan is None or self._active_plan.pool is not pool):
             raise ValueError("inference: the running sequences are not in a %d-slot pool at %dx%d; assign fake_B_prev = None "
                              "to restart" % (S, W, H))
-        fp = self._frame_plan(H, W, in_ch, has_inst, False, u8, B=K, pool=S)
+        fp = self._frame_plan(H, W, in_ch, has_inst, False, u8, B=K, pool=S, frames_u8=img)
         if self.is_first_frame:
             rst = list(act)
             for w in pool.windows:
@@ -743,7 +779,10 @@ class Vid2VidModelG(BaseModel):
         fp.run()
         # one indexed copy of the dense rows into the zero tensors: fresh tensors per frame, idle rows zero
         index = fp.row_slot.long()
-        fake.index_copy_(0, index, fp.out["fake_B"])
+        if img:
+            fake = fp.out["image"].clone()
+        else:
+            fake.index_copy_(0, index, fp.out["fake_B"])
         last = fp.out["real_A_last"]
         real_A_last.index_copy_(0, index, last if K > 1 else last.unsqueeze(0))
         return fake, real_A_last

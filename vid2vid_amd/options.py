@@ -30,7 +30,9 @@ _DEFAULTS = dict(
     fix_update_fixed_params=False,   # True: update_fixed_params rebuilds the captured optimizer over all scales (the reference's
                                      # evident intent); False: the reference's observable behaviour (models/base_model.py docstring)
     compact_streams=False,    # multi-stream inference replays a plan with one row per ACTIVE stream (stream pool)
-    ema_decay=0.0,            # training: > 0 keeps an exponential moving average of the generator's weights inside the Adam step
+    frames_u8=False,          # inference returns uint8 (B,H,W,3) images written by the frame plan's last launch instead of the fp32
+                              # fake_B planes; an idle stream's image is zero bytes; read per call
+    ema_decay=0.0,           # training: > 0 keeps an exponential moving average of the generator's weights inside the Adam step
                               # and saves it as '<label>_net_G<s>_ema.pth' (DESIGN 3.17); 0 = off, nothing changes
     use_ema=False,            # inference: load '<epoch>_net_G<s>_ema.pth' instead of '<epoch>_net_G<s>.pth'
 )

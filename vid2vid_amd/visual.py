@@ -6,6 +6,7 @@ device and only the uint8 HWC image crosses PCIe; `AsyncImageWriter` encodes / w
 does not stall a generator that runs at hundreds of frames per second.
 
     tensor2im(t, normalize=True)  -> uint8 device tensor (H, W, C) or (H, W) for one plane      (util/util.py:48-71)
+    tensor2im_batch(t, normalize) -> uint8 device tensor (B, H, W, C) of (B, C, H, W), one launch for all samples
     tensor2label(t, n_label)      -> uint8 device tensor (H, W, 3)                              (util/util.py:73-87)
     tensor2flow(t)                -> uint8 device tensor (H, W, 3), HSV-coded flow picture      (util/util.py:89-107)
     to_numpy(img)                 -> what the reference's function returns (numpy uint8)
@@ -74,6 +75,19 @@ def tensor2im(image_tensor, normalize=True):
     check(lib.v2v_tensor2im(C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), Cc, H, W, int(bool(normalize)), _stream(x)),
           "tensor2im")
     return out[:, :, 0] if Cc == 1 else out
+
+
+def tensor2im_batch(image_tensor, normalize=True):
+    """tensor2im of every sample of (B, C, H, W), C <= 4, in one launch (v2v_frames_u8): uint8 (B, H, W, C), sample b bit for bit
+    tensor2im(image_tensor[b]).  (Frame plans of a model with opt.frames_u8 record the same launch as their last op.)"""
+    if image_tensor.dim() != 4:
+        raise ValueError("tensor2im_batch expects (B, C, H, W), got %s" % (tuple(image_tensor.shape),))
+    x = image_tensor.detach().float().contiguous()
+    B, Cc, H, W = x.shape
+    out = torch.empty((B, H, W, Cc), dtype=torch.uint8, device=x.device)
+    check(lib.v2v_frames_u8(C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), None, None, B, B, Cc, H, W, int(bool(normalize)),
+                            _stream(x)), "frames_u8")
+    return out
 
 
 def tensor2label(output, n_label):
