@@ -429,24 +429,27 @@ struct PrologueArgs {
     int N = 1;       // v2v_frame_prologue_batch: blockIdx.y is the sample, every tensor has a leading N (dense)
 };
 
-// BATCH = false is the one-sample kernel as it always was (sample 0, no offsets)
-template <typename T, typename LT, typename IT, bool BATCH>
-__global__ __launch_bounds__(256) void frame_prologue_kernel(const PrologueArgs a) {
+// Row (sample) nb of the prologue: the one body of frame_prologue_kernel and frame_prologue_pool_kernel, which differ only in
+// the row `wrow` of a.window ([rows][win_C][H][W], may be null: codes and mask only) that is row nb's window.  Every other tensor is
+// dense with a leading N.  The kernels pass blockDim.x and gridDim.x in: read in a __device__ function they compile to the
+// non-uniform-workgroup path (a vector load, the stride in VGPRs: + 1 us per launch).
+template <typename T, typename LT, typename IT>
+__device__ __forceinline__ void frame_prologue_row(const PrologueArgs& a, long long nb, long long wrow, unsigned block_dim,
+                                                   unsigned grid_dim) {
     constexpr int VEC = ElemTraits<T>::VEC;
     const long long hw = (long long)a.H * a.W;
     const long long ncode = hw * a.T;
     const int vpr = a.window ? a.c_stride / VEC : 0;
     const long long total = ncode + hw * vpr;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    const long long nb = BATCH ? (long long)blockIdx.y : 0ll;
+    const long long stride = (long long)grid_dim * block_dim;
     const LT* labels = reinterpret_cast<const LT*>(a.labels) + nb * ncode;
     const IT* inst = a.inst ? reinterpret_cast<const IT*>(a.inst) + nb * ncode : nullptr;
     unsigned char* codes = a.codes + nb * ncode;
     float* mask = a.mask ? a.mask + nb * hw : nullptr;
-    const float* window = a.window ? a.window + nb * a.win_C * hw : nullptr;
+    const float* window = a.window ? a.window + wrow * a.win_C * hw : nullptr;
     float* last = a.last ? a.last + nb * a.last_C * hw : nullptr;
     T* y = reinterpret_cast<T*>(a.packed) + nb * hw * a.c_stride;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+    for (long long e = (long long)blockIdx.x * block_dim + threadIdx.x; e < total; e += stride) {
         if (e < ncode) {
             const long long t = e / hw, q = e - t * hw;
             const int lab = (int)labels[e];
@@ -483,6 +486,13 @@ __global__ __launch_bounds__(256) void frame_prologue_kernel(const PrologueArgs 
     }
 }
 
+// BATCH = false is the one-sample kernel as it always was (sample 0, no offsets)
+template <typename T, typename LT, typename IT, bool BATCH>
+__global__ __launch_bounds__(256) void frame_prologue_kernel(const PrologueArgs a) {
+    const long long nb = BATCH ? (long long)blockIdx.y : 0ll;
+    frame_prologue_row<T, LT, IT>(a, nb, nb, blockDim.x, gridDim.x);
+}
+
 struct PrologueOp : Op {
     PrologueArgs a; int dtype; int in_u8;
     int launch(hipStream_t s) override {
@@ -507,63 +517,16 @@ struct PrologueOp : Op {
 
 // Stream pool (v2v_frame_prologue_pool): the batched kernel above over K dense rows whose window is slot row_slot[row] of the pool
 // [S][win_C][H][W].  The slot word is loaded once per workgroup (blockIdx.y is the row: wave-uniform) and branched on; a row whose
-// word is outside [0, S) returns before it reads or writes anything.  Per element the expressions and the store order are those
-// of frame_prologue_kernel.
+// word is outside [0, S) returns before it reads or writes anything.  The row's work is frame_prologue_row.
 struct ProloguePoolArgs { PrologueArgs p; const int* row_slot; int S; };
 
 template <typename T, typename LT, typename IT>
 __global__ __launch_bounds__(256) void frame_prologue_pool_kernel(const ProloguePoolArgs s) {
     const PrologueArgs& a = s.p;
-    constexpr int VEC = ElemTraits<T>::VEC;
-    const long long nb = (long long)blockIdx.y;
-    const int slot = s.row_slot[nb];
+    const int slot = s.row_slot[blockIdx.y];
     if (slot < 0 || slot >= s.S) return;
-    const long long hw = (long long)a.H * a.W;
-    const long long ncode = hw * a.T;
-    const int vpr = a.c_stride / VEC;
-    const long long total = ncode + hw * vpr;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    const LT* labels = reinterpret_cast<const LT*>(a.labels) + nb * ncode;
-    const IT* inst = a.inst ? reinterpret_cast<const IT*>(a.inst) + nb * ncode : nullptr;
-    unsigned char* codes = a.codes + nb * ncode;
-    float* mask = a.mask ? a.mask + nb * hw : nullptr;
-    const float* window = a.window + (long long)slot * a.win_C * hw;
-    float* last = a.last ? a.last + nb * a.last_C * hw : nullptr;
-    T* y = reinterpret_cast<T*>(a.packed) + nb * hw * a.c_stride;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
-        if (e < ncode) {
-            const long long t = e / hw, q = e - t * hw;
-            const int lab = (int)labels[e];
-            bool edge = false;
-            if (inst) {
-                const int py = (int)(q / a.W), px = (int)(q - (long long)py * a.W);
-                const IT* ip = inst + t * hw;
-                const IT ctr = ip[q];
-                if (px > 0)       edge |= ip[q - 1] != ctr;
-                if (px < a.W - 1) edge |= ip[q + 1] != ctr;
-                if (py > 0)       edge |= ip[q - a.W] != ctr;
-                if (py < a.H - 1) edge |= ip[q + a.W] != ctr;
-            }
-            codes[e] = (unsigned char)(((unsigned)lab < (unsigned)a.label_nc ? lab : 127) | (edge ? 128 : 0));
-            if (mask && t == a.T - 1) {
-                float m = 0.f;
-                for (int i = 0; i < a.n_fg; ++i) m += (a.fg[i] == lab) ? 1.f : 0.f;
-                mask[q] = fminf(fmaxf(m, 0.f), 1.f);
-            }
-        } else {
-            const long long v = e - ncode;
-            const long long pix = v % hw;
-            const int cv = (int)(v / hw);
-            float vals[VEC];
-#pragma unroll
-            for (int q = 0; q < VEC; ++q) {
-                const int c = cv * VEC + q;
-                vals[q] = c < a.win_C ? window[c * hw + pix] : 0.f;
-                if (last && c < a.win_C && c >= a.win_C - a.last_C) last[(c - (a.win_C - a.last_C)) * hw + pix] = vals[q];
-            }
-            store_vec(y, pix * a.c_stride + cv * VEC, vals);
-        }
-    }
+    __builtin_assume(a.window != nullptr);          // the entry point refuses a null pool
+    frame_prologue_row<T, LT, IT>(a, blockIdx.y, slot, blockDim.x, gridDim.x);
 }
 
 struct ProloguePoolOp : Op {
@@ -732,47 +695,60 @@ struct WarpArgs {
     float* roll = nullptr; int roll_slots = 0;
 };
 
-// ROLLB: the rolled windows of N samples ([N][slots][C][H][W]); false is the kernel as it always was
+// Pixel `pix` of row n, every channel: the one body of warp_blend_kernel, warp_blend_slots_kernel and warp_blend_pool_kernel.
+// do_warp false is the raw-only frame (no flow / weight read, no gather, fin = raw).  `win` is this row's window
+// [slots][C][H][W], rolled by the thread that stores img_final, or null.
+__device__ __forceinline__ void warp_blend_pixel(const WarpArgs& a, long long n, long long pix, bool do_warp, float* win) {
+    const long long hw = (long long)a.H * a.W;
+    const int y = (int)(pix / a.W), x = (int)(pix - (long long)y * a.W);
+    int x0 = 0, y0 = 0; float wx = 0.f, wy = 0.f;
+    float wgt = 1.f;
+    if (do_warp) {
+        const float fx = a.flow[(n * 2 + 0) * hw + pix], fy = a.flow[(n * 2 + 1) * hw + pix];
+        bilinear_setup(fx, fy, a.gx[x], a.gy[y], a.H, a.W, a.align_corners, x0, y0, wx, wy);
+        wgt = a.weight[n * hw + pix];
+    }
+    const float m = a.fg ? a.mask[n * hw + pix] : 0.f;
+    for (int c = 0; c < a.C; ++c) {
+        const long long o = (n * a.C + c) * hw + pix;
+        float raw = a.img_raw[o];
+        float fin = raw;
+        if (do_warp) {
+            const float wv = bilinear_fetch(a.prev + (n * a.C + c) * hw, a.H, a.W, x0, y0, wx, wy);
+            if (a.img_warp) a.img_warp[o] = wv;
+            fin = raw * wgt + wv * (1.f - wgt);
+        }
+        if (a.fg) {
+            const float f = a.fg[o];
+            fin = f * m + fin * (1.f - m);
+            raw = f * m + raw * (1.f - m);
+            a.img_raw[o] = raw;
+        }
+        a.img_final[o] = fin;
+        if (win) {
+            float* w = win + c * hw + pix;
+            const long long slot = (long long)a.C * hw;
+            for (int k = 0; k + 1 < a.roll_slots; ++k) w[k * slot] = w[(k + 1) * slot];
+            w[(a.roll_slots - 1) * slot] = fin;
+        }
+    }
+}
+
+// row n's window of a batch layout [N][slots][C][H][W], null without a window
+__device__ __forceinline__ float* warp_row_window(const WarpArgs& a, long long n) {
+    return a.roll ? a.roll + n * a.roll_slots * a.C * a.H * a.W : nullptr;
+}
+
+// ROLLB: the rolled windows of N samples ([N][slots][C][H][W]).  false (no window, or one sample's) keeps the per-element window
+// offset out of the single-sequence frame's launch: 11.3 us against 10.7 us at 512x256 without the split.
 template <bool ROLLB>
 __global__ __launch_bounds__(256) void warp_blend_kernel(const WarpArgs a) {
     const long long hw = (long long)a.H * a.W;
     const long long total = (long long)a.N * hw;
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
-        const long long n = e / hw, pix = e - n * hw;
-        const int y = (int)(pix / a.W), x = (int)(pix - (long long)y * a.W);
-        int x0 = 0, y0 = 0; float wx = 0.f, wy = 0.f;
-        const bool do_warp = a.flow != nullptr;
-        float wgt = 1.f;
-        if (do_warp) {
-            const float fx = a.flow[(n * 2 + 0) * hw + pix], fy = a.flow[(n * 2 + 1) * hw + pix];
-            bilinear_setup(fx, fy, a.gx[x], a.gy[y], a.H, a.W, a.align_corners, x0, y0, wx, wy);
-            wgt = a.weight[n * hw + pix];
-        }
-        const float m = a.fg ? a.mask[n * hw + pix] : 0.f;
-        for (int c = 0; c < a.C; ++c) {
-            const long long o = (n * a.C + c) * hw + pix;
-            float raw = a.img_raw[o];
-            float fin = raw;
-            if (do_warp) {
-                const float wv = bilinear_fetch(a.prev + (n * a.C + c) * hw, a.H, a.W, x0, y0, wx, wy);
-                if (a.img_warp) a.img_warp[o] = wv;
-                fin = raw * wgt + wv * (1.f - wgt);
-            }
-            if (a.fg) {
-                const float f = a.fg[o];
-                fin = f * m + fin * (1.f - m);
-                raw = f * m + raw * (1.f - m);
-                a.img_raw[o] = raw;
-            }
-            a.img_final[o] = fin;
-            if (a.roll) {                               // sample n's window: [slots][C][H][W]
-                float* w = a.roll + (ROLLB ? (n * a.roll_slots * a.C + c) * hw + pix : o);
-                const long long slot = (long long)a.C * hw;
-                for (int k = 0; k + 1 < a.roll_slots; ++k) w[k * slot] = w[(k + 1) * slot];
-                w[(a.roll_slots - 1) * slot] = fin;
-            }
-        }
+        const long long n = e / hw;
+        warp_blend_pixel(a, n, e - n * hw, a.flow != nullptr, ROLLB ? warp_row_window(a, n) : a.roll);
     }
 }
 
@@ -789,9 +765,9 @@ struct WarpOp : Op {
 
 // Stream slots (v2v_warp_blend_slots): the batched rolling blend with one mode word per sample, loaded once per element and
 // BRANCHED on (never a multiplication by a mask: an idle sample's NaN must not reach its zero row).
-//   0 steady    the arithmetic and store order of warp_blend_kernel<true>, expression for expression
-//   1 raw only  first frame of a sequence without a first image: no flow / weight read, no gather, fin = raw; the foreground
-//               blend and the roll as in mode 0 (what the kernel above does with flow == nullptr)
+//   0 steady    warp_blend_pixel, as warp_blend_kernel runs it
+//   1 raw only  first frame of a sequence without a first image: warp_blend_pixel with do_warp false (what the kernel above does
+//               with flow == nullptr)
 //   other       idle: img_final = 0, nothing else of the sample is read or written (img_raw, img_warp, flow, the window)
 // a.roll may be null (the window is then rolled by window_roll_slots_kernel); it always has the batch layout [N][slots][C][H][W].
 struct WarpSlotArgs { WarpArgs w; const int* mode; };
@@ -808,39 +784,7 @@ __global__ __launch_bounds__(256) void warp_blend_slots_kernel(const WarpSlotArg
             for (int c = 0; c < a.C; ++c) a.img_final[(n * a.C + c) * hw + pix] = 0.f;
             continue;
         }
-        const int y = (int)(pix / a.W), x = (int)(pix - (long long)y * a.W);
-        int x0 = 0, y0 = 0; float wx = 0.f, wy = 0.f;
-        const bool do_warp = a.flow != nullptr && md == 0;
-        float wgt = 1.f;
-        if (do_warp) {
-            const float fx = a.flow[(n * 2 + 0) * hw + pix], fy = a.flow[(n * 2 + 1) * hw + pix];
-            bilinear_setup(fx, fy, a.gx[x], a.gy[y], a.H, a.W, a.align_corners, x0, y0, wx, wy);
-            wgt = a.weight[n * hw + pix];
-        }
-        const float m = a.fg ? a.mask[n * hw + pix] : 0.f;
-        for (int c = 0; c < a.C; ++c) {
-            const long long o = (n * a.C + c) * hw + pix;
-            float raw = a.img_raw[o];
-            float fin = raw;
-            if (do_warp) {
-                const float wv = bilinear_fetch(a.prev + (n * a.C + c) * hw, a.H, a.W, x0, y0, wx, wy);
-                if (a.img_warp) a.img_warp[o] = wv;
-                fin = raw * wgt + wv * (1.f - wgt);
-            }
-            if (a.fg) {
-                const float f = a.fg[o];
-                fin = f * m + fin * (1.f - m);
-                raw = f * m + raw * (1.f - m);
-                a.img_raw[o] = raw;
-            }
-            a.img_final[o] = fin;
-            if (a.roll) {                               // sample n's window: [slots][C][H][W]
-                float* w = a.roll + (n * a.roll_slots * a.C + c) * hw + pix;
-                const long long slot = (long long)a.C * hw;
-                for (int k = 0; k + 1 < a.roll_slots; ++k) w[k * slot] = w[(k + 1) * slot];
-                w[(a.roll_slots - 1) * slot] = fin;
-            }
-        }
+        warp_blend_pixel(a, n, pix, a.flow != nullptr && md == 0, warp_row_window(a, n));
     }
 }
 
@@ -881,8 +825,8 @@ struct WindowRollOp : Op {
 
 // Stream pool (v2v_warp_blend_pool): warp_blend_slots_kernel over K dense rows that roll slot row_slot[row] of the pool
 // [S][slots][C][H][W].  blockIdx.y is the row, so its two words (slot, mode) are loaded once per workgroup and are wave-uniform.
-// mode 0 and 1 as in warp_blend_slots_kernel, expression for expression; a row of any other mode, or whose slot is outside [0, S),
-// returns before it reads or writes anything.
+// mode 0 and 1 as in warp_blend_slots_kernel (warp_blend_pixel); a row of any other mode, or whose slot is outside [0, S), returns
+// before it reads or writes anything.
 struct WarpPoolArgs { WarpArgs w; const int* mode; const int* row_slot; int S; };
 
 __global__ __launch_bounds__(256) void warp_blend_pool_kernel(const WarpPoolArgs s) {
@@ -894,38 +838,8 @@ __global__ __launch_bounds__(256) void warp_blend_pool_kernel(const WarpPoolArgs
     const long long stride = (long long)gridDim.x * blockDim.x;
     const bool do_warp = a.flow != nullptr && md == 0;
     float* const win = a.roll + (long long)slot * a.roll_slots * a.C * hw;      // this row's window: [slots][C][H][W]
-    for (long long pix = (long long)blockIdx.x * blockDim.x + threadIdx.x; pix < hw; pix += stride) {
-        const int y = (int)(pix / a.W), x = (int)(pix - (long long)y * a.W);
-        int x0 = 0, y0 = 0; float wx = 0.f, wy = 0.f;
-        float wgt = 1.f;
-        if (do_warp) {
-            const float fx = a.flow[(n * 2 + 0) * hw + pix], fy = a.flow[(n * 2 + 1) * hw + pix];
-            bilinear_setup(fx, fy, a.gx[x], a.gy[y], a.H, a.W, a.align_corners, x0, y0, wx, wy);
-            wgt = a.weight[n * hw + pix];
-        }
-        const float m = a.fg ? a.mask[n * hw + pix] : 0.f;
-        for (int c = 0; c < a.C; ++c) {
-            const long long o = (n * a.C + c) * hw + pix;
-            float raw = a.img_raw[o];
-            float fin = raw;
-            if (do_warp) {
-                const float wv = bilinear_fetch(a.prev + (n * a.C + c) * hw, a.H, a.W, x0, y0, wx, wy);
-                if (a.img_warp) a.img_warp[o] = wv;
-                fin = raw * wgt + wv * (1.f - wgt);
-            }
-            if (a.fg) {
-                const float f = a.fg[o];
-                fin = f * m + fin * (1.f - m);
-                raw = f * m + raw * (1.f - m);
-                a.img_raw[o] = raw;
-            }
-            a.img_final[o] = fin;
-            float* w = win + c * hw + pix;
-            const long long sl = (long long)a.C * hw;
-            for (int k = 0; k + 1 < a.roll_slots; ++k) w[k * sl] = w[(k + 1) * sl];
-            w[(a.roll_slots - 1) * sl] = fin;
-        }
-    }
+    for (long long pix = (long long)blockIdx.x * blockDim.x + threadIdx.x; pix < hw; pix += stride)
+        warp_blend_pixel(a, n, pix, do_warp, win);
 }
 
 struct WarpPoolOp : Op {
@@ -1573,6 +1487,24 @@ extern "C" int v2v_warp_blend(float* img_raw, const float* flow, const float* we
     return submit(std::move(op), stream);
 }
 
+// The checks of the rolling blend entry point `who`: pointers, sizes, and that no row's gather source or frame buffer lies inside
+// any of the `win_rows` windows [slots][C][H][W] at a.roll, whichever rows roll them (`what` names them in the message).  a.roll
+// may be null only where `need_window` is false.
+static bool warp_roll_args_ok(const char* who, const WarpArgs& a, bool need_window, long long win_rows, const char* what) {
+    if (!a.img_raw || !a.img_final || (a.flow && (!a.weight || !a.prev || !a.gx || !a.gy)) || (a.fg && !a.mask) ||
+        (need_window && !a.roll) || (a.roll && a.roll_slots < 1) || a.N < 1 || win_rows < 1 || a.C < 1 || a.H < 1 || a.W < 1) {
+        set_error("%s: bad argument", who); return false;
+    }
+    if (!a.roll) return true;
+    const float* wend = a.roll + win_rows * a.roll_slots * a.C * a.H * a.W;
+    const long long frame = (long long)a.N * a.C * a.H * a.W;
+    auto overlaps = [&](const float* p) { return p && p + frame > a.roll && p < wend; };
+    if (overlaps(a.prev) || overlaps(a.img_final) || overlaps(a.img_raw) || overlaps(a.fg)) {
+        set_error("%s: the %s must not overlap the gather source or the frame buffers", who, what); return false;
+    }
+    return true;
+}
+
 extern "C" int v2v_warp_blend_roll(float* img_raw, const float* flow, const float* weight, const float* prev,
                                    const float* fg, const float* mask, float* img_final, float* img_warp,
                                    const float* gx, const float* gy, float* window, int32_t slots,
@@ -1585,20 +1517,9 @@ extern "C" int v2v_warp_blend_roll_batch(float* img_raw, const float* flow, cons
                                          const float* fg, const float* mask, float* img_final, float* img_warp,
                                          const float* gx, const float* gy, float* window, int32_t slots,
                                          int32_t N, int32_t C, int32_t H, int32_t W, int32_t align_corners, void* stream) {
-    if (!img_raw || !img_final || (flow && (!weight || !prev || !gx || !gy)) || (fg && !mask) || !window || slots < 1 ||
-        N < 1 || C < 1 || H < 1 || W < 1) {
-        set_error("warp_blend_roll: bad argument"); return V2V_EINVAL;
-    }
-    // the frame buffers of ALL samples against the windows of ALL samples: no sample's gather source may lie in any rolled window
-    const float* wend = window + (long long)N * slots * C * H * W;
-    const long long frame = (long long)N * C * H * W;
-    auto overlaps = [&](const float* p) { return p && p + frame > window && p < wend; };
-    if (overlaps(prev) || overlaps(img_final) || overlaps(img_raw) || overlaps(fg)) {
-        set_error("warp_blend_roll: the rolled window must not overlap the gather source or the frame buffers"); return V2V_EINVAL;
-    }
     auto op = std::make_unique<WarpOp>();
-    op->a = WarpArgs{img_raw, flow, weight, prev, fg, mask, img_final, img_warp, gx, gy, N, C, H, W, align_corners};
-    op->a.roll = window; op->a.roll_slots = slots;
+    op->a = WarpArgs{img_raw, flow, weight, prev, fg, mask, img_final, img_warp, gx, gy, N, C, H, W, align_corners, window, slots};
+    if (!warp_roll_args_ok("warp_blend_roll", op->a, true, N, "rolled window")) return V2V_EINVAL;
     return submit(std::move(op), stream);
 }
 
@@ -1607,22 +1528,11 @@ extern "C" int v2v_warp_blend_slots(float* img_raw, const float* flow, const flo
                                     const float* gx, const float* gy, float* window, int32_t slots, const int32_t* mode,
                                     int32_t N, int32_t C, int32_t H, int32_t W, int32_t align_corners, void* stream) {
     if (!mode) { set_error("warp_blend_slots: null mode"); return V2V_EINVAL; }
-    if (!img_raw || !img_final || (flow && (!weight || !prev || !gx || !gy)) || (fg && !mask) || (window && slots < 1) ||
-        N < 1 || C < 1 || H < 1 || W < 1) {
-        set_error("warp_blend_slots: bad argument"); return V2V_EINVAL;
-    }
-    if (window) {       // as v2v_warp_blend_roll_batch: no sample's gather source or frame buffer inside any rolled window
-        const float* wend = window + (long long)N * slots * C * H * W;
-        const long long frame = (long long)N * C * H * W;
-        auto overlaps = [&](const float* p) { return p && p + frame > window && p < wend; };
-        if (overlaps(prev) || overlaps(img_final) || overlaps(img_raw) || overlaps(fg)) {
-            set_error("warp_blend_slots: the rolled window must not overlap the gather source or the frame buffers"); return V2V_EINVAL;
-        }
-    }
     auto op = std::make_unique<WarpSlotsOp>();
-    op->a.w = WarpArgs{img_raw, flow, weight, prev, fg, mask, img_final, img_warp, gx, gy, N, C, H, W, align_corners};
-    op->a.w.roll = window; op->a.w.roll_slots = window ? slots : 0;
+    op->a.w = WarpArgs{img_raw, flow, weight, prev, fg, mask, img_final, img_warp, gx, gy, N, C, H, W, align_corners, window, slots};
     op->a.mode = mode;
+    if (!warp_roll_args_ok("warp_blend_slots", op->a.w, false, N, "rolled window")) return V2V_EINVAL;
+    if (!window) op->a.w.roll_slots = 0;
     return submit(std::move(op), stream);
 }
 
@@ -1647,21 +1557,12 @@ extern "C" int v2v_warp_blend_pool(float* img_raw, const float* flow, const floa
                                    const int32_t* row_slot, int32_t K, int32_t S, int32_t C, int32_t H, int32_t W,
                                    int32_t align_corners, void* stream) {
     if (!mode || !row_slot) { set_error("warp_blend_pool: null %s", !mode ? "mode" : "row_slot"); return V2V_EINVAL; }
-    if (!img_raw || !img_final || (flow && (!weight || !prev || !gx || !gy)) || (fg && !mask) || !window || slots < 1 ||
-        K < 1 || K > 65535 || S < 1 || C < 1 || H < 1 || W < 1) {
-        set_error("warp_blend_pool: bad argument"); return V2V_EINVAL;
-    }
-    // as v2v_warp_blend_roll_batch, against the WHOLE pool: any slot may be rolled by this launch
-    const float* wend = window + (long long)S * slots * C * H * W;
-    const long long frame = (long long)K * C * H * W;
-    auto overlaps = [&](const float* p) { return p && p + frame > window && p < wend; };
-    if (overlaps(prev) || overlaps(img_final) || overlaps(img_raw) || overlaps(fg)) {
-        set_error("warp_blend_pool: the pool must not overlap the gather source or the frame buffers"); return V2V_EINVAL;
-    }
     auto op = std::make_unique<WarpPoolOp>();
-    op->a.w = WarpArgs{img_raw, flow, weight, prev, fg, mask, img_final, img_warp, gx, gy, K, C, H, W, align_corners};
-    op->a.w.roll = window; op->a.w.roll_slots = slots;
+    op->a.w = WarpArgs{img_raw, flow, weight, prev, fg, mask, img_final, img_warp, gx, gy, K, C, H, W, align_corners, window, slots};
     op->a.mode = mode; op->a.row_slot = row_slot; op->a.S = S;
+    if (K > 65535) { set_error("warp_blend_pool: bad argument"); return V2V_EINVAL; }      // K is the launch's gridDim.y
+    // against the WHOLE pool: any slot may be rolled by this launch
+    if (!warp_roll_args_ok("warp_blend_pool", op->a.w, true, S, "pool")) return V2V_EINVAL;
     return submit(std::move(op), stream);
 }
 
@@ -1690,6 +1591,21 @@ extern "C" int v2v_window_scatter_pool(float* pool, const float* dense, const in
     return window_pool_copy("window_scatter_pool", pool, dense, true, row_slot, K, S, slots, C, H, W, stream);
 }
 
+// The checks of the prologue entry point `who` behind its row count; the window pack's only where there is a window.
+static bool prologue_args_ok(const char* who, const PrologueArgs& a, int in_u8, int dtype) {
+    const int vec = dtype == V2V_BF16 ? 8 : 4;
+    if (!a.labels || !a.codes || a.T < 1 || a.H < 1 || a.W < 1 || a.label_nc < 1 || a.label_nc > 126 || (in_u8 != 0 && in_u8 != 1) ||
+        (dtype != V2V_F32 && dtype != V2V_BF16) || a.n_fg < 0 || (a.mask && a.n_fg > 0 && !a.fg) ||
+        (in_u8 ? ((uintptr_t)a.inst & 3) != 0 : (((uintptr_t)a.labels | (uintptr_t)a.inst) & 3) != 0)) {
+        set_error("%s: bad argument (label_nc <= 126)", who); return false;
+    }
+    if (a.window && (!a.packed || a.win_C < 1 || a.c_stride % vec != 0 || a.win_C > a.c_stride || ((uintptr_t)a.packed & 15) != 0 ||
+                     (a.last && (a.last_C < 1 || a.last_C > a.win_C)))) {
+        set_error("%s: bad window pack argument", who); return false;
+    }
+    return true;
+}
+
 extern "C" int v2v_frame_prologue(const void* labels, const void* inst, int32_t in_u8, uint8_t* codes, float* mask,
                                   const int32_t* fg_labels_dev, int32_t n_fg, int32_t T, int32_t H, int32_t W, int32_t label_nc,
                                   const float* window, int32_t win_C, void* packed, int32_t c_stride, float* last, int32_t last_C,
@@ -1702,22 +1618,13 @@ extern "C" int v2v_frame_prologue_batch(const void* labels, const void* inst, in
                                         const int32_t* fg_labels_dev, int32_t n_fg, int32_t N, int32_t T, int32_t H, int32_t W,
                                         int32_t label_nc, const float* window, int32_t win_C, void* packed, int32_t c_stride,
                                         float* last, int32_t last_C, int32_t dtype, void* stream) {
-    const int vec = dtype == V2V_BF16 ? 8 : 4;
     if (N < 1 || N > 65535) { set_error("frame_prologue: bad sample count %d", N); return V2V_EINVAL; }
-    if (!labels || !codes || T < 1 || H < 1 || W < 1 || label_nc < 1 || label_nc > 126 || (in_u8 != 0 && in_u8 != 1) ||
-        (dtype != V2V_F32 && dtype != V2V_BF16) || n_fg < 0 || (mask && n_fg > 0 && !fg_labels_dev) ||
-        (in_u8 ? ((uintptr_t)inst & 3) != 0 : (((uintptr_t)labels | (uintptr_t)inst) & 3) != 0)) {
-        set_error("frame_prologue: bad argument (label_nc <= 126)"); return V2V_EINVAL;
-    }
-    if (window && (!packed || win_C < 1 || c_stride % vec != 0 || win_C > c_stride || ((uintptr_t)packed & 15) != 0 ||
-                   (last && (last_C < 1 || last_C > win_C)))) {
-        set_error("frame_prologue: bad window pack argument"); return V2V_EINVAL;
-    }
     auto op = std::make_unique<PrologueOp>();
-    op->a = PrologueArgs{labels, inst, codes, mask, fg_labels_dev, n_fg, window, window ? packed : nullptr, window ? last : nullptr,
-                         T, H, W, label_nc, win_C, c_stride, last_C};
-    op->a.N = N;
+    op->a = PrologueArgs{labels, inst, codes, mask, fg_labels_dev, n_fg, window, packed, last,
+                         T, H, W, label_nc, win_C, c_stride, last_C, N};
     op->dtype = dtype; op->in_u8 = in_u8;
+    if (!prologue_args_ok("frame_prologue", op->a, in_u8, dtype)) return V2V_EINVAL;
+    if (!window) op->a.packed = op->a.last = nullptr;
     return submit(std::move(op), stream);
 }
 
@@ -1725,24 +1632,14 @@ extern "C" int v2v_frame_prologue_pool(const void* labels, const void* inst, int
                                        const int32_t* fg_labels_dev, int32_t n_fg, int32_t K, int32_t T, int32_t H, int32_t W,
                                        int32_t label_nc, const float* window, int32_t S, const int32_t* row_slot, int32_t win_C,
                                        void* packed, int32_t c_stride, float* last, int32_t last_C, int32_t dtype, void* stream) {
-    const int vec = dtype == V2V_BF16 ? 8 : 4;
     if (!row_slot || !window) { set_error("frame_prologue_pool: null %s", !row_slot ? "row_slot" : "window"); return V2V_EINVAL; }
     if (K < 1 || K > 65535 || S < 1) { set_error("frame_prologue_pool: bad row count %d / pool size %d", K, S); return V2V_EINVAL; }
-    if (!labels || !codes || T < 1 || H < 1 || W < 1 || label_nc < 1 || label_nc > 126 || (in_u8 != 0 && in_u8 != 1) ||
-        (dtype != V2V_F32 && dtype != V2V_BF16) || n_fg < 0 || (mask && n_fg > 0 && !fg_labels_dev) ||
-        (in_u8 ? ((uintptr_t)inst & 3) != 0 : (((uintptr_t)labels | (uintptr_t)inst) & 3) != 0)) {
-        set_error("frame_prologue_pool: bad argument (label_nc <= 126)"); return V2V_EINVAL;
-    }
-    if (!packed || win_C < 1 || c_stride % vec != 0 || win_C > c_stride || ((uintptr_t)packed & 15) != 0 ||
-        (last && (last_C < 1 || last_C > win_C))) {
-        set_error("frame_prologue_pool: bad window pack argument"); return V2V_EINVAL;
-    }
     auto op = std::make_unique<ProloguePoolOp>();
     op->a.p = PrologueArgs{labels, inst, codes, mask, fg_labels_dev, n_fg, window, packed, last,
-                           T, H, W, label_nc, win_C, c_stride, last_C};
-    op->a.p.N = K;
+                           T, H, W, label_nc, win_C, c_stride, last_C, K};
     op->a.row_slot = row_slot; op->a.S = S;
     op->dtype = dtype; op->in_u8 = in_u8;
+    if (!prologue_args_ok("frame_prologue_pool", op->a.p, in_u8, dtype)) return V2V_EINVAL;
     return submit(std::move(op), stream);
 }
 

@@ -846,21 +846,13 @@ class Engine:
             cs = packed.Cs
             if last_C:
                 last = self.empty_f32(N, last_C, H, W)
-        if row_slot is not None:
-            check(lib.v2v_frame_prologue_pool(_ptr(labels), _ptr(inst), int(u8), _ptr(codes), _ptr(mask), _ptr(fg),
-                                              0 if fg is None else fg.numel(), N, T, H, W, src.label_nc, _ptr(window),
-                                              window.shape[0], _ptr(row_slot), win_C, _ptr(packed.t), cs, _ptr(last), last_C,
-                                              self.dtype, _stream()), "frame_prologue_pool")
-        elif N == 1:
-            check(lib.v2v_frame_prologue(_ptr(labels), _ptr(inst), int(u8), _ptr(codes), _ptr(mask), _ptr(fg),
-                                         0 if fg is None else fg.numel(), T, H, W, src.label_nc, _ptr(window), win_C,
-                                         _ptr(None if packed is None else packed.t), cs, _ptr(last), last_C, self.dtype, _stream()),
-                  "frame_prologue")
-        else:
-            check(lib.v2v_frame_prologue_batch(_ptr(labels), _ptr(inst), int(u8), _ptr(codes), _ptr(mask), _ptr(fg),
-                                               0 if fg is None else fg.numel(), N, T, H, W, src.label_nc, _ptr(window), win_C,
-                                               _ptr(None if packed is None else packed.t), cs, _ptr(last), last_C, self.dtype,
-                                               _stream()), "frame_prologue_batch")
+        # one sample is the batch entry point with N = 1 (what v2v_frame_prologue itself calls); the pool's takes S and row_slot
+        # behind the window
+        entry, pool = ("frame_prologue_batch", ()) if row_slot is None else ("frame_prologue_pool", (window.shape[0], _ptr(row_slot)))
+        check(getattr(lib, "v2v_" + entry)(_ptr(labels), _ptr(inst), int(u8), _ptr(codes), _ptr(mask), _ptr(fg),
+                                           0 if fg is None else fg.numel(), N, T, H, W, src.label_nc, _ptr(window), *pool, win_C,
+                                           _ptr(None if packed is None else packed.t), cs, _ptr(last), last_C, self.dtype,
+                                           _stream()), entry)
         self.label("frame_prologue")
         src.codes = codes
         x0 = Act(torch.empty((N, H, W, pad_channels(T * per, self.dtype)), dtype=self.tdtype, device="meta"), T * per, onehot=src)
@@ -2078,51 +2070,31 @@ class Engine:
         warp = self.empty_f32(N, Cc, H, W) if (want_warp and flow is not None) else None
         for t in (gx, gy):
             self._keep(t)
-        if row_slot is not None:
-            if (slot_mode is None or roll is None or roll.dim() != 5 or tuple(roll.shape[2:]) != (Cc, H, W)
-                    or roll.dtype != torch.float32 or not roll.is_contiguous()
-                    or any(t.dtype != torch.int32 or tuple(t.shape) != (N,) or not t.is_contiguous() for t in (slot_mode, row_slot))):
-                raise ValueError("warp_blend: a pooled blend rolls an fp32 pool (S, slots, C, H, W) under int32 slot_mode, row_slot (N,)")
-            self._keep(slot_mode)
-            self._keep(row_slot)
-            check(lib.v2v_warp_blend_pool(_ptr(img_raw), _ptr(flow), _ptr(weight), _ptr(prev), _ptr(fg), _ptr(mask),
-                                          _ptr(final), _ptr(warp), _ptr(gx), _ptr(gy), _ptr(roll), roll.shape[1], _ptr(slot_mode),
-                                          _ptr(row_slot), N, roll.shape[0], Cc, H, W, int(self.align_corners), _stream()),
-                  "warp_blend_pool")
-            self.label("warp_blend")
-            return final, warp
-        if slot_mode is not None:
-            if slot_mode.dtype != torch.int32 or tuple(slot_mode.shape) != (N,) or not slot_mode.is_contiguous():
-                raise ValueError("warp_blend: slot_mode is int32 (N,)")
-            if roll is not None and (roll.dim() != 5 or tuple(roll.shape[2:]) != (Cc, H, W) or roll.shape[0] != N
-                                     or roll.dtype != torch.float32 or not roll.is_contiguous()):
-                raise ValueError("warp_blend: the rolled windows are fp32 (N, slots, C, H, W)")
-            self._keep(slot_mode)
-            check(lib.v2v_warp_blend_slots(_ptr(img_raw), _ptr(flow), _ptr(weight), _ptr(prev), _ptr(fg), _ptr(mask),
-                                           _ptr(final), _ptr(warp), _ptr(gx), _ptr(gy), _ptr(roll),
-                                           0 if roll is None else roll.shape[1], _ptr(slot_mode), N, Cc, H, W,
-                                           int(self.align_corners), _stream()), "warp_blend_slots")
-            self.label("warp_blend")
-            return final, warp
-        if roll is not None and roll.dim() == 5:
-            if tuple(roll.shape[2:]) != (Cc, H, W) or roll.shape[0] != N or roll.dtype != torch.float32 or not roll.is_contiguous():
-                raise ValueError("warp_blend: the rolled windows are fp32 (N, slots, C, H, W)")
-            check(lib.v2v_warp_blend_roll_batch(_ptr(img_raw), _ptr(flow), _ptr(weight), _ptr(prev), _ptr(fg), _ptr(mask),
-                                                _ptr(final), _ptr(warp), _ptr(gx), _ptr(gy), _ptr(roll), roll.shape[1], N, Cc, H, W,
-                                                int(self.align_corners), _stream()), "warp_blend_roll_batch")
-            self.label("warp_blend")
-            return final, warp
+        words = [t for t in (slot_mode, row_slot) if t is not None]
+        if row_slot is not None and (slot_mode is None or roll is None):
+            raise ValueError("warp_blend: a pooled blend rolls an fp32 pool (S, slots, C, H, W) under int32 slot_mode, row_slot (N,)")
+        if any(t.dtype != torch.int32 or tuple(t.shape) != (N,) or not t.is_contiguous() for t in words):
+            raise ValueError("warp_blend: slot_mode and row_slot are int32 (N,)")
         if roll is not None:
-            if N != 1 or tuple(roll.shape[1:]) != (Cc, H, W) or roll.dtype != torch.float32 or not roll.is_contiguous():
-                raise ValueError("warp_blend: the rolled window is fp32 (slots, C, H, W) of one sample")
-            check(lib.v2v_warp_blend_roll(_ptr(img_raw), _ptr(flow), _ptr(weight), _ptr(prev), _ptr(fg), _ptr(mask),
-                                          _ptr(final), _ptr(warp), _ptr(gx), _ptr(gy), _ptr(roll), roll.shape[0], Cc, H, W,
-                                          int(self.align_corners), _stream()), "warp_blend_roll")
-            self.label("warp_blend")
-            return final, warp
-        check(lib.v2v_warp_blend(_ptr(img_raw), _ptr(flow), _ptr(weight), _ptr(prev), _ptr(fg), _ptr(mask),
-                                 _ptr(final), _ptr(warp), _ptr(gx), _ptr(gy), N, Cc, H, W,
-                                 int(self.align_corners), _stream()), "warp_blend")
+            lead = tuple(roll.shape[:-4])        # () one sample's window, (N,) one per stream, (S,) the pool row_slot indexes
+            if (roll.dim() < 4 or tuple(roll.shape[-3:]) != (Cc, H, W) or roll.dtype != torch.float32 or not roll.is_contiguous()
+                    or not (len(lead) == 1 if row_slot is not None else lead == (N,) or (lead == () and N == 1 and not words))):
+                raise ValueError("warp_blend: the rolled window is fp32 (slots, C, H, W) of one sample, (N, slots, C, H, W) of N "
+                                 "streams, or with row_slot the pool (S, slots, C, H, W)")
+        for t in words:
+            self._keep(t)
+        # the entry point, and what it takes between gy and C
+        win = (_ptr(roll), 0 if roll is None else roll.shape[-4])
+        if row_slot is not None:
+            entry, extra = "warp_blend_pool", win + (_ptr(slot_mode), _ptr(row_slot), N, roll.shape[0])
+        elif slot_mode is not None:
+            entry, extra = "warp_blend_slots", win + (_ptr(slot_mode), N)
+        elif roll is None:
+            entry, extra = "warp_blend", (N,)
+        else:
+            entry, extra = ("warp_blend_roll", win) if roll.dim() == 4 else ("warp_blend_roll_batch", win + (N,))
+        check(getattr(lib, "v2v_" + entry)(_ptr(img_raw), _ptr(flow), _ptr(weight), _ptr(prev), _ptr(fg), _ptr(mask), _ptr(final),
+                                           _ptr(warp), _ptr(gx), _ptr(gy), *extra, Cc, H, W, int(self.align_corners), _stream()), entry)
         self.label("warp_blend")
         return final, warp
 

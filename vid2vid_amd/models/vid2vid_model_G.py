@@ -109,24 +109,22 @@ class _FramePlan:
         else:
             self.prev = [torch.zeros(*lead, tG - 1, opt.output_nc, H >> si, W >> si, dtype=torch.float32, device=dev)
                          for si in range(S)]
-        self.slot_mode = self.slot_mode_host = self._slot_mode_copied = None
+        # the plan's int32 words, refreshed per call by set_words: slot_mode (B,) of a slot plan, row_slot | row_mode of a pool plan
+        self.slot_mode = self.row_slot = self._words = self._words_host = self._words_copied = None
         if self.slots:
-            self.slot_mode = torch.zeros(B, dtype=torch.int32, device=dev)
-            self.slot_mode_host = torch.zeros(B, dtype=torch.int32)
-            if dev.type == "cuda":
-                self.slot_mode_host = self.slot_mode_host.pin_memory()
+            self.slot_mode = self._words = torch.zeros(B, dtype=torch.int32, device=dev)
             # does the finest generator end in the blend launch (which writes an idle stream's row of zeros)?
             self.blend_launch = getattr(model, "netG" + str(S - 1)).blends_in_tail()
-        self.row_slot = self._rows = self._rows_host = None
         if pool is not None:
             # row_slot | row_mode in one buffer: one 8*K-byte copy per call.  Identity slots until the first call (the warm-up and
             # tuning replays of _build run on valid, distinct slots; _frame_plan puts the windows back behind them)
-            self._rows = torch.cat([torch.arange(B, dtype=torch.int32), torch.zeros(B, dtype=torch.int32)]).to(dev)
-            self._rows_host = torch.zeros(2 * B, dtype=torch.int32)
-            if dev.type == "cuda":
-                self._rows_host = self._rows_host.pin_memory()
-            self.row_slot, self.slot_mode = self._rows[:B], self._rows[B:]
+            self._words = torch.cat([torch.arange(B, dtype=torch.int32), torch.zeros(B, dtype=torch.int32)]).to(dev)
+            self.row_slot, self.slot_mode = self._words[:B], self._words[B:]
             self.dense = {}              # si -> (K, tG-1, 3, h, w): the gathered windows of the paths off the rolling blend
+        if self._words is not None:
+            self._words_host = torch.zeros(self._words.numel(), dtype=torch.int32)
+            if dev.type == "cuda":
+                self._words_host = self._words_host.pin_memory()
         self.out = {}
         # independent towers / branches on parallel plan lanes (parallel hipGraph paths); opt.lanes or V2V_LANES
         self.lanes = bool(int(getattr(opt, "lanes", os.environ.get("V2V_LANES", "1")))) and use_graph
@@ -409,26 +407,17 @@ class _FramePlan:
         # compute_mask on a pooled (fractional) one-hot pyramid level: clamp(sum of fg channels)
         return self.eng.fg_mask(x, (tG - 1) * per, self.model.opt.fg_labels)
 
-    def set_slot_modes(self, modes):
-        """Refresh slot_mode for the next replay: one 4*B-byte asynchronous copy from pinned host memory, like the label buffers.
-        (The host buffer is rewritten only after the previous copy out of it has completed.)"""
-        if self._slot_mode_copied is not None:
-            self._slot_mode_copied.synchronize()
-        self.slot_mode_host.copy_(torch.as_tensor(modes, dtype=torch.int32))
-        self.slot_mode.copy_(self.slot_mode_host, non_blocking=True)
-        if self.slot_mode.device.type == "cuda":
-            self._slot_mode_copied = torch.cuda.Event()
-            self._slot_mode_copied.record()
-
-    def set_rows(self, rows, modes):
-        """Pool plans: refresh row_slot and row_mode for the next replay, as set_slot_modes does (one asynchronous copy)."""
-        if self._slot_mode_copied is not None:
-            self._slot_mode_copied.synchronize()
-        self._rows_host.copy_(torch.as_tensor(list(rows) + list(modes), dtype=torch.int32))
-        self._rows.copy_(self._rows_host, non_blocking=True)
-        if self._rows.device.type == "cuda":
-            self._slot_mode_copied = torch.cuda.Event()
-            self._slot_mode_copied.record()
+    def set_words(self, words):
+        """Refresh the plan's words for the next replay -- a slot plan's B modes, a pool plan's K slots followed by its K modes --
+        by one asynchronous copy from pinned host memory, like the label buffers.  (The host buffer is rewritten only after the
+        previous copy out of it has completed.)"""
+        if self._words_copied is not None:
+            self._words_copied.synchronize()
+        self._words_host.copy_(torch.as_tensor(words, dtype=torch.int32))
+        self._words.copy_(self._words_host, non_blocking=True)
+        if self._words.device.type == "cuda":
+            self._words_copied = torch.cuda.Event()
+            self._words_copied.record()
 
     def run(self):
         if self.eng.record_only:
@@ -657,21 +646,11 @@ class Vid2VidModelG(BaseModel):
                 return self._inference_slots(input_A, input_B, inst_A, act, rst, has_inst, u8, img)
             use_raw_only = bool(opt.no_first_img and self.is_first_frame)
             fp = self._frame_plan(H, W, in_ch, has_inst, use_raw_only, u8, B, frames_u8=img)
-            dev = self.device
-            # ---- stage inputs (H2D or D2D) into the plan's static buffers; pinned host tensors copy asynchronously ----
-            if fp.label_mode:
-                fp.labels.copy_((input_A[0, :tG, 0] if B == 1 else input_A[:, :tG, 0]).to(dev, fp.labels.dtype, non_blocking=True))
-                if has_inst:
-                    fp.inst.copy_((inst_A[0, :tG, 0] if B == 1 else inst_A[:, :tG, 0]).to(dev, fp.inst.dtype, non_blocking=True))
-            else:
-                fp.raw_in.copy_(input_A[:, :tG].reshape(B, tG * in_ch, H, W).to(dev, torch.float32, non_blocking=True))
+            self._stage_inputs(fp, input_A, inst_A, has_inst, list(range(B)))
             if self.is_first_frame:
-                first = self.generate_first_frame(input_A, input_B, inst_A)     # list per scale (tG-1,3,h,w) / (B,tG-1,3,h,w)
-                for si in range(self.n_scales):
-                    fp.prev[si].copy_(first[si])
-            elif self._active_plan is not fp:
-                for si in range(self.n_scales):                                  # e.g. first-frame plan -> steady plan
-                    fp.prev[si].copy_(self._active_plan.prev[si])
+                self._seed_windows(fp.prev, input_A, input_B, inst_A)
+            else:
+                self._carry_windows(fp)                                          # e.g. first-frame plan -> steady plan
             self._active_plan = fp
             self.fake_B_prev = fp.prev
             fp.run()
@@ -679,43 +658,68 @@ class Vid2VidModelG(BaseModel):
             # next replay; a caller collecting a clip must not see every entry alias the last frame)
             return fp.out["image" if img else "fake_B"].clone(), fp.out["real_A_last"].clone()
 
+    def _stage_inputs(self, fp, input_A, inst_A, has_inst, rows, in_place=False):
+        """Stage (H2D or D2D) the newest tG frames of the streams `rows` (ascending) into fp's static buffers; the other streams'
+        rows of the inputs are not read.  Pinned host tensors copy asynchronously.
+        in_place False: they become the plan's rows 0..len(rows)-1, by one copy per tensor (plain and pool plans).
+        in_place True: stream b is row b of the plan (slot plans) -- one copy per tensor when every stream is named, else per row."""
+        tG, dev = self.opt.n_frames_G, self.device
+        every = len(rows) == input_A.shape[0] > 1
+        if in_place and not every:
+            pairs = [(b, b) for b in rows]                                   # (rows of the inputs, rows of the plan)
+        else:
+            pairs = [(slice(None) if every else rows[0] if len(rows) == 1 else rows, Ellipsis)]
+        for src, dst in pairs:
+            if fp.label_mode:
+                fp.labels[dst].copy_(input_A[src, :tG, 0].to(dev, fp.labels.dtype, non_blocking=True))
+                if has_inst:
+                    fp.inst[dst].copy_(inst_A[src, :tG, 0].to(dev, fp.inst.dtype, non_blocking=True))
+            else:
+                raw = fp.raw_in[dst]
+                raw.copy_(input_A[src, :tG].reshape(raw.shape).to(dev, torch.float32, non_blocking=True))
+
+    def _seed_windows(self, windows, input_A, input_B, inst_A, new=None):
+        """Seed `windows` (a list per scale) from generate_first_frame: whole (new=None: the first frame of every sequence), or
+        the streams in the list `new` alone, from their rows of the inputs alone (windows then have a leading stream dimension)."""
+        if new is None:
+            first = self.generate_first_frame(input_A, input_B, inst_A)         # list per scale (tG-1,3,h,w) / (B,tG-1,3,h,w)
+        elif new:
+            first = self.generate_first_frame(input_A[new], None if input_B is None else input_B[new],
+                                              None if inst_A is None else inst_A[new])
+        else:
+            return
+        for si in range(self.n_scales):
+            if new is None:
+                windows[si].copy_(first[si])
+            else:
+                for k, b in enumerate(new):
+                    windows[si][b].copy_(first[si] if len(new) == 1 else first[si][k])
+
+    def _carry_windows(self, fp):
+        """fp continues the running sequences: unless it ran last itself, it gets the windows of the plan that did."""
+        if self._active_plan is not fp:
+            for si in range(self.n_scales):
+                fp.prev[si].copy_(self._active_plan.prev[si])
+
     def _inference_slots(self, input_A, input_B, inst_A, act, rst, has_inst, u8, img=False):
         """One replay of the slot plan (B > 1).  act / rst: B bools.  On the first frame of the model
         (fake_B_prev = None) every active stream starts a sequence and the windows of the idle ones are zero.
         img (opt.frames_u8): the uint8 images the plan's last launch wrote, idle rows zero, instead of fake_B."""
-        opt, dev = self.opt, self.device
-        tG = opt.n_frames_G
+        opt = self.opt
         B, _, in_ch, H, W = input_A.shape
         fp = self._frame_plan(H, W, in_ch, has_inst, False, u8, B, slots=True, frames_u8=img)
         if self.is_first_frame:
             rst = list(act)
-        # ---- stage the rows of the active streams; an idle stream's rows are not read (the buffers keep its last valid rows) ----
+        # the rows of the active streams, each in its place (the buffers keep an idle stream's last valid rows)
         rows = [b for b in range(B) if act[b]]
-        for sel in ([slice(None)] if len(rows) == B else rows):
-            if fp.label_mode:
-                fp.labels[sel].copy_(input_A[sel, :tG, 0].to(dev, fp.labels.dtype, non_blocking=True))
-                if has_inst:
-                    fp.inst[sel].copy_(inst_A[sel, :tG, 0].to(dev, fp.inst.dtype, non_blocking=True))
-            else:
-                fp.raw_in[sel].copy_(input_A[sel, :tG].reshape(fp.raw_in[sel].shape).to(dev, torch.float32, non_blocking=True))
-        # ---- windows ----
+        self._stage_inputs(fp, input_A, inst_A, has_inst, rows, in_place=True)
         if self.is_first_frame:
             for si in range(self.n_scales):
                 fp.prev[si].zero_()
-        elif self._active_plan is not fp:
-            for si in range(self.n_scales):                                      # plain plan -> slot plan
-                fp.prev[si].copy_(self._active_plan.prev[si])
-        new = [b for b in range(B) if rst[b]]
-        if new:
-            first = self.generate_first_frame(input_A[new], None if input_B is None else input_B[new],
-                                              None if inst_A is None else inst_A[new])
-            for si in range(self.n_scales):
-                if len(new) == 1:
-                    fp.prev[si][new[0]].copy_(first[si])
-                else:
-                    for k, b in enumerate(new):
-                        fp.prev[si][b].copy_(first[si][k])
-        fp.set_slot_modes([2 if not act[b] else (1 if (rst[b] and opt.no_first_img) else 0) for b in range(B)])
+        else:
+            self._carry_windows(fp)                                              # plain plan -> slot plan
+        self._seed_windows(fp.prev, input_A, input_B, inst_A, [b for b in range(B) if rst[b]])
+        fp.set_words([2 if not act[b] else (1 if (rst[b] and opt.no_first_img) else 0) for b in range(B)])
         self._active_plan = fp
         self.fake_B_prev = fp.prev
         fp.run()
@@ -732,7 +736,6 @@ class Vid2VidModelG(BaseModel):
         img (opt.frames_u8): the plan's last launch delivers the (S,H,W,3) uint8 images, idle slots zero; no zero tensor and no
         indexed copy for the frames."""
         opt, dev = self.opt, self.device
-        tG = opt.n_frames_G
         S, _, in_ch, H, W = input_A.shape
         rows = [b for b in range(S) if act[b]]
         K = len(rows)
@@ -753,26 +756,9 @@ class Vid2VidModelG(BaseModel):
             rst = list(act)
             for w in pool.windows:
                 w.zero_()
-        # ---- stage the rows of the active streams straight into the dense rows; an idle stream's rows are not read ----
-        sel = rows[0] if K == 1 else (slice(None) if K == S else rows)
-        if fp.label_mode:
-            fp.labels.copy_(input_A[sel, :tG, 0].to(dev, fp.labels.dtype, non_blocking=True))
-            if has_inst:
-                fp.inst.copy_(inst_A[sel, :tG, 0].to(dev, fp.inst.dtype, non_blocking=True))
-        else:
-            fp.raw_in.copy_(input_A[sel, :tG].reshape(fp.raw_in.shape).to(dev, torch.float32, non_blocking=True))
-        # ---- windows: a restarted slot is re-seeded on its rows alone ----
-        new = [b for b in range(S) if rst[b]]
-        if new:
-            first = self.generate_first_frame(input_A[new], None if input_B is None else input_B[new],
-                                              None if inst_A is None else inst_A[new])
-            for si in range(self.n_scales):
-                if len(new) == 1:
-                    pool.windows[si][new[0]].copy_(first[si])
-                else:
-                    for k, b in enumerate(new):
-                        pool.windows[si][b].copy_(first[si][k])
-        fp.set_rows(rows, [1 if (rst[b] and opt.no_first_img) else 0 for b in rows])
+        self._stage_inputs(fp, input_A, inst_A, has_inst, rows)           # the active streams' rows, straight into the dense rows
+        self._seed_windows(pool.windows, input_A, input_B, inst_A, [b for b in range(S) if rst[b]])
+        fp.set_words(rows + [1 if (rst[b] and opt.no_first_img) else 0 for b in rows])
         pool.idle = [b for b in range(S) if not act[b]]
         self._active_plan = fp
         self.fake_B_prev = pool.windows
