@@ -596,6 +596,26 @@ int v2v_frame_prologue_batch(const void* labels, const void* inst, int32_t in_u8
                              int32_t label_nc, const float* window, int32_t win_C, void* packed, int32_t c_stride,
                              float* last, int32_t last_C, int32_t dtype, void* stream);
 
+/* Head of an inference frame whose inputs are 8-bit images (label_nc == 0: pose2body, edge2face), in ONE launch.  win is the input
+ * window, uint8 HWC [N][T][H][W][Cin], oldest frame first; lut fp32 [Cin][256] holds the loader's per-byte value transform of every
+ * channel (ToTensor + Normalize(0.5, 0.5), data/base_dataset.py:148-157; the DensePose part-index rescale of
+ * data/pose_dataset.py:44 for that channel), so the decoded value of a byte b of channel c is lut[c][b], bit for bit.
+ *   x0         NHWC activation dtype [N][H][W][c_stride], channel t * Cin + c = lut[c][win[n][t][y][x][c]], converted as
+ *              v2v_pack_nchw_to_nhwc converts, pad channels T Cin .. c_stride - 1 zero: bit for bit that pack of the decoded planes;
+ *   real_last  planar fp32 [N][Cin][H][W], the newest frame as x0 holds it: bit for bit v2v_unpack_nhwc_to_nchw of x0's channels
+ *              (T - 1) Cin .., i.e. the decoded values, rounded to bf16 when dtype is V2V_BF16 (what the fp32-input frame plan
+ *              returns as real_A[0][0, -1], models/vid2vid_model_G.py:209);
+ *   packed, last (with window != NULL, planar fp32 [N][win_C][H][W]): as v2v_frame_prologue_batch writes them, by the same code.
+ * advance != 0: the launch also moves the window on, win[n][t] <- win[n][t + 1] for t < T - 1 (slot T - 1 keeps its bytes): the
+ * caller stages only the newest frame into slot T - 1 before the next launch (the test loader decodes one new frame per step,
+ * data/pose_dataset.py:38).  The bytes of a pixel are read and written back by the workgroup that owns the pixel.
+ * V2V_EINVAL for a null win / lut / x0 / real_last, Cin outside 1..32 (the table is held in LDS), N outside 1..65535, T Cin >
+ * c_stride, c_stride or win_c_stride no multiple of the 16-byte vector, win / lut / x0 / packed not 16-byte aligned, T frames that
+ * do not fit in LDS beside the table, overlapping buffers.  Recorded into a plan as op "image_prologue". */
+int v2v_image_prologue(uint8_t* win, const float* lut, int32_t advance, void* x0, int32_t c_stride, float* real_last,
+                       int32_t N, int32_t T, int32_t H, int32_t W, int32_t Cin, const float* window, int32_t win_C,
+                       void* packed, int32_t win_c_stride, float* last, int32_t last_C, int32_t dtype, void* stream);
+
 /* Stream pool (a K-row plan serving K of S slots): row_slot[K], int32 in device memory, read when the launch runs (a frame plan
  * refreshes it per replay), names the slot of the pool that dense row k works on.  The word is loaded once per row (the row is a
  * grid dimension) and branched on.  A row whose word is outside [0, S) does nothing: no window is read or written and the row's

@@ -858,6 +858,52 @@ class Engine:
         x0 = Act(torch.empty((N, H, W, pad_channels(T * per, self.dtype)), dtype=self.tdtype, device="meta"), T * per, onehot=src)
         return x0, mask, packed, last
 
+    def image_prologue(self, win, lut, window=None, last_C=0, advance=True):
+        """Head of an inference frame whose inputs are 8-bit images, in one launch (v2v_image_prologue).  win: the
+        input window, uint8 (N, T, H, W, Cin), oldest frame first; lut: fp32 (Cin, 256), the decoded value of every byte of every
+        channel.  Returns (x0, real_last, packed Act or None, last or None): x0 the NHWC stem input, channel t * Cin + c =
+        lut[c][win[n, t, y, x, c]], bit for bit Engine.pack of the decoded planes; real_last fp32 (N, Cin, H, W), the newest
+        frame as x0 holds it (Engine.unpack of its channels: the decoded values, bf16-rounded in a bf16 engine); with `window`, planar fp32 (N, C, H, W), its NHWC pack and an fp32 copy of its last `last_C` planes as
+        Engine.frame_prologue returns them.  advance: the launch also moves the window on by a frame, win[:, t] <- win[:, t + 1]
+        (slot T - 1 is left as it is), so the caller stages only the newest frame before the next launch."""
+        if not isinstance(win, torch.Tensor) or win.dtype != torch.uint8:
+            raise TypeError("image_prologue: the input window is uint8 (N, T, H, W, Cin)")
+        if not isinstance(lut, torch.Tensor) or lut.dtype != torch.float32:
+            raise TypeError("image_prologue: the table is fp32 (Cin, 256)")
+        if win.dim() != 5 or not win.is_contiguous():
+            raise ValueError("image_prologue: the input window is contiguous uint8 (N, T, H, W, Cin)")
+        N, T, H, W, Cin = win.shape
+        if Cin > 32:
+            raise ValueError("image_prologue: %d input channels; the table of at most 32 channels is held in LDS" % Cin)
+        if tuple(lut.shape) != (Cin, 256) or not lut.is_contiguous() or lut.device != win.device:
+            raise ValueError("image_prologue: the table is contiguous fp32 (%d, 256) on the window's device, got %s"
+                             % (Cin, tuple(lut.shape)))
+        if window is not None:
+            if window.dtype != torch.float32:
+                raise TypeError("image_prologue: the generated-frame window is fp32 (N, C, H, W)")
+            if window.dim() != 4 or tuple(window.shape[::3]) != (N, W) or window.shape[2] != H or not window.is_contiguous():
+                raise ValueError("image_prologue: %d image streams at %dx%d, window %s" % (N, W, H, tuple(window.shape)))
+            if not 0 <= last_C <= window.shape[1]:
+                raise ValueError("image_prologue: last_C = %d of a window of %d planes" % (last_C, window.shape[1]))
+        self._keep(win)
+        self._keep(lut)
+        x0 = self.empty_act(N, H, W, T * Cin)
+        real_last = self.empty_f32(N, Cin, H, W)
+        packed = last = None
+        win_C = cs = 0
+        if window is not None:
+            self._keep(window)
+            win_C = window.shape[1]
+            packed = self.empty_act(N, H, W, win_C)
+            cs = packed.Cs
+            if last_C:
+                last = self.empty_f32(N, last_C, H, W)
+        check(lib.v2v_image_prologue(_ptr(win), _ptr(lut), int(bool(advance)), _ptr(x0.t), x0.Cs, _ptr(real_last), N, T, H, W, Cin,
+                                     _ptr(window), win_C, _ptr(None if packed is None else packed.t), cs, _ptr(last), last_C,
+                                     self.dtype, _stream()), "image_prologue")
+        self.label("image_prologue")
+        return x0, real_last, packed, last
+
     def onehot_conv(self, x, conv, want_stats=True, label="", fin=None):
         """Raw fp32 NHWC output + statistics rows of the stem convolution, computed from the label maps behind `x`.
         Returns (raw, rows, (N, OH, OW)) like conv(..., OUT_RAW_F32_NHWC, want_stats=True).  fin = (norm, ss): the

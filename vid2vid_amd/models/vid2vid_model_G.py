@@ -75,10 +75,13 @@ class _FramePlan:
     windows, row k works on slot row_slot[k] under row_mode[k] (0 steady, 1 raw-only first frame; int32 (K,), refreshed per call
     like slot_mode).  K == 1 emits the batch-1 body, K > 1 the per-stream one; only the head and the tail know about slots.
     frames_u8: the plan's last launch converts its fake_B rows into `out["image"]`, uint8 (B, H, W, 3) -- (S, H, W, 3)
-    for a pool plan -- under the plan's own slot_mode / row_slot words: idle streams and slots come out as zero bytes."""
+    for a pool plan -- under the plan's own slot_mode / row_slot words: idle streams and slots come out as zero bytes.
+    inputs_u8 (label_nc == 0, plain plans): instead of raw_in the plan owns `win_u8`, the uint8 HWC input window
+    (B, tG, H, W, in_ch), and `lut`, fp32 (in_ch, 256); its first launch (Engine.image_prologue) decodes the window into the stem
+    input and real_A_last and moves it on by a frame, so a call stages the newest frame only."""
 
     def __init__(self, model, H, W, in_ch, has_inst, use_raw_only, use_graph=True, u8=False, B=1, slots=False, pool=None,
-                 frames_u8=False):
+                 frames_u8=False, inputs_u8=False):
         opt, eng = model.opt, model.engine
         self.model, self.eng = model, eng
         self.H, self.W, self.use_raw_only, self.B = H, W, use_raw_only, B
@@ -93,6 +96,9 @@ class _FramePlan:
         tG, S = opt.n_frames_G, model.n_scales
         self.label_mode = opt.label_nc != 0
         dev = eng.device
+        self.win_u8 = self.lut = self._lut_src = None
+        if inputs_u8 and (self.label_mode or self.slots or pool is not None):
+            raise ValueError("uint8 image inputs (opt.inputs_u8) go with label_nc == 0 and plain plans")
         # ---- static inputs ----
         if self.label_mode:
             # fp32-encoded integers (the reference loader's format), or uint8 labels + int32 instance ids (SURVEY 8f-2:
@@ -102,7 +108,10 @@ class _FramePlan:
             self.raw_in = None
         else:
             self.labels = self.inst = None
-            self.raw_in = torch.zeros(B, tG * in_ch, H, W, dtype=torch.float32, device=dev)
+            self.raw_in = None if inputs_u8 else torch.zeros(B, tG * in_ch, H, W, dtype=torch.float32, device=dev)
+            if inputs_u8:
+                self.win_u8 = torch.zeros(B, tG, H, W, in_ch, dtype=torch.uint8, device=dev)
+                self.lut = torch.zeros(in_ch, 256, dtype=torch.float32, device=dev)
         # fake_B_prev[si]: (tG-1, 3, h, w) per scale, si = 0 finest  (reference :228, :248-250); (B, tG-1, 3, h, w) at B > 1
         if pool is not None:
             self.prev = pool.windows
@@ -283,6 +292,13 @@ class _FramePlan:
             else:
                 x0, mask0 = eng.encode_labels(self.labels, self.inst, tG, H, W, opt.label_nc, opt.fg_labels, opt.fg,
                                               chunk_stride=S > 1, source=src)   # fine-scale stems (cout <= 32): LDS-patch 7x7 kernel
+        elif self.win_u8 is not None:
+            # one spatial scale: the decode, the window pack and (where the generator ends in the blend) the rolls are the head and
+            # tail launches, as for label maps
+            if S == 1 and not opt.fg and hasattr(m.netG0, "rolls_in_tail"):
+                return self._emit_image_head()
+            x0, real_last, _, _ = eng.image_prologue(self.win_u8, self.lut)
+            mask0 = x1 = None
         else:
             x0, mask0, x1 = eng.pack(self.raw_in), None, None
         xs, masks = [x0], [mask0]
@@ -313,6 +329,8 @@ class _FramePlan:
         # real_A[0][0, -1]: encoded last label frame, returned for visualisation (:209)
         if self.label_mode:      # straight from the label map: coalesced planar writes, no NHWC -> NCHW transpose
             self.out["real_A_last"] = self._real_A_last()
+        elif self.win_u8 is not None:      # the prologue decoded the newest frame into planes itself
+            self.out["real_A_last"] = real_last[0] if B == 1 else real_last
         else:
             last = Act(x0.t[..., (tG - 1) * per:], per)
             last = eng.unpack(last)
@@ -359,6 +377,27 @@ class _FramePlan:
             self._roll(prev, fake_B)
             if self.pool is not None:
                 eng.window_scatter(self.prev[0], prev, self.row_slot)
+        self.out["flow0"], self.out["weight0"], self.out["raw0"] = flow, weight, raw
+        self.out["fake_B"] = fake_B
+        self._emit_image()
+        self.conv_log = list(eng.conv_log)
+
+    def _emit_image_head(self):
+        """The frame of a uint8-input plan at one spatial scale: image_prologue | towers ... | warp_blend.  The prologue writes
+        the stem input, real_A_last, the pack of the generated-frame window and the warp's gather source, and moves the input
+        window on; the blend rolls the generated-frame window where the generator ends in it.  No pack, unpack or copy launch."""
+        m, eng, opt = self.model, self.eng, self.model.opt
+        H, W, B = self.H, self.W, self.B
+        netG = m.netG0
+        prev = self.prev[0]
+        x0, real_last, prev_act, last = eng.image_prologue(self.win_u8, self.lut, window=prev.view(B, -1, H, W),
+                                                           last_C=opt.output_nc)
+        self.out["real_A_last"] = real_last[0] if B == 1 else real_last
+        roll = prev if netG.rolls_in_tail(self.use_raw_only) else None
+        fake_B, flow, weight, raw, _, _, _ = netG.emit(eng, x0, prev_act, last, None, None, None, None, self.use_raw_only,
+                                                       tag="G0", roll=roll)
+        if roll is None:
+            self._roll(prev, fake_B)
         self.out["flow0"], self.out["weight0"], self.out["raw0"] = flow, weight, raw
         self.out["fake_B"] = fake_B
         self._emit_image()
@@ -508,11 +547,13 @@ class Vid2VidModelG(BaseModel):
                         views[p].copy_(saved[name])
 
     # ------------------------------------------------------------------ inference
-    def _frame_plan(self, H, W, in_ch, has_inst, use_raw_only, u8=False, B=1, slots=False, pool=None, frames_u8=False):
+    def _frame_plan(self, H, W, in_ch, has_inst, use_raw_only, u8=False, B=1, slots=False, pool=None, frames_u8=False,
+                    inputs_u8=False):
         """pool: the slot capacity S of a pool plan with B rows; its key ends in ("pool", S).
-        frames_u8: the plan ends in the uint8 image launch; only then its key gains a last field "frames_u8"."""
+        frames_u8: the plan ends in the uint8 image launch; only then its key gains a field "frames_u8".
+        inputs_u8: the plan starts with the uint8 image head; only then its key gains a last field "inputs_u8"."""
         key = (H, W, in_ch, has_inst, use_raw_only, self.precision, u8, B) + (("slots",) if slots else ()) + \
-              ((("pool", pool),) if pool else ()) + (("frames_u8",) if frames_u8 else ())
+              ((("pool", pool),) if pool else ()) + (("frames_u8",) if frames_u8 else ()) + (("inputs_u8",) if inputs_u8 else ())
         fp = self._plans.get(key)
         if fp is None:
             self.engine.refresh_weights()
@@ -521,7 +562,7 @@ class Vid2VidModelG(BaseModel):
             saved = [w.clone() for w in windows.windows] if pool else []
             fp = _FramePlan(self, H, W, in_ch, has_inst, use_raw_only,
                             use_graph=getattr(self.opt, "use_graph", True), u8=u8, B=B, slots=slots, pool=windows,
-                            frames_u8=frames_u8)
+                            frames_u8=frames_u8, inputs_u8=inputs_u8)
             for w, keep in zip(windows.windows if pool else [], saved):
                 w.copy_(keep)
             self._plans[key] = fp
@@ -594,13 +635,26 @@ class Vid2VidModelG(BaseModel):
         of fake_B: image[b] == visual.tensor2im(fake_B[b]) for every active stream b, fake_B being what the same call returns with
         the option off, and an idle stream's image is all ZERO bytes (not the 127 that zero planes convert to).  The images are
         written by the last launch of the frame plan; real_A_last, fake_B_prev and every other state are as with the option off,
-        and the option may change between the calls of running sequences."""
+        and the option may change between the calls of running sequences.
+        opt.inputs_u8 (read per call; label_nc == 0 only): input_A is torch.uint8 (B,t,H,W,in_ch) -- 8-bit HWC frames as
+        a decoder delivers them, on host or device -- with t == n_frames_G, the whole window (required on the first call of a
+        sequence, allowed on any), or t == 1, the newest frame alone (only while a sequence started that way is running: the
+        plan keeps the older frames and moves them on itself).  The frame plan's first launch decodes byte b of channel c to
+        opt.input_lut[c][b] (fp32 (in_ch,256); None: visual.input_lut(in_ch), the reference loader's ToTensor + Normalize); every
+        result equals, bit for bit, what the call returns on those decoded fp32 planes with the option off.  Anything else --
+        another t, fp32 input_A, a label model, in_ch > 32, a table of another shape, restart= / active= or opt.compact_streams
+        (slot and pool plans take fp32 inputs) -- is a ValueError that leaves the running sequences as they are."""
         opt = self.opt
         tG = opt.n_frames_G
         with torch.no_grad():
-            B, t_in, in_ch, H, W = input_A.shape
-            if t_in < tG:
-                raise ValueError("inference needs n_frames_G=%d label frames, got %d" % (tG, t_in))
+            in_u8 = bool(getattr(opt, "inputs_u8", False))
+            if in_u8:
+                lut = self._check_inputs_u8(input_A, restart, active)
+                B, t_in, H, W, in_ch = input_A.shape
+            else:
+                B, t_in, in_ch, H, W = input_A.shape
+                if t_in < tG:
+                    raise ValueError("inference needs n_frames_G=%d label frames, got %d" % (tG, t_in))
             for name, t in (("inst_A", inst_A if opt.use_instance else None), ("input_B", input_B)):
                 if t is not None and t.shape[0] != B:
                     raise ValueError("inference: input_A holds %d sequence(s), %s %d" % (B, name, t.shape[0]))
@@ -645,12 +699,18 @@ class Vid2VidModelG(BaseModel):
                     act, rst = [True] * B, [False] * B
                 return self._inference_slots(input_A, input_B, inst_A, act, rst, has_inst, u8, img)
             use_raw_only = bool(opt.no_first_img and self.is_first_frame)
-            fp = self._frame_plan(H, W, in_ch, has_inst, use_raw_only, u8, B, frames_u8=img)
-            self._stage_inputs(fp, input_A, inst_A, has_inst, list(range(B)))
+            fp = self._frame_plan(H, W, in_ch, has_inst, use_raw_only, u8, B, frames_u8=img, inputs_u8=in_u8)
+            if not in_u8:
+                self._stage_inputs(fp, input_A, inst_A, has_inst, list(range(B)))
             if self.is_first_frame:
-                self._seed_windows(fp.prev, input_A, input_B, inst_A)
+                # (uint8 inputs: the first-frame generators read fp32 planes -- decoded once per sequence, off the hot path)
+                from ..visual import decode_inputs
+                planes = decode_inputs(input_A.to(self.device), lut) if in_u8 else input_A
+                self._seed_windows(fp.prev, planes, input_B, inst_A)
             else:
                 self._carry_windows(fp)                                          # e.g. first-frame plan -> steady plan
+            if in_u8:                    # behind the carry: the newest frame lands in the window the sequence has reached
+                self._stage_inputs_u8(fp, input_A, lut)
             self._active_plan = fp
             self.fake_B_prev = fp.prev
             fp.run()
@@ -678,6 +738,54 @@ class Vid2VidModelG(BaseModel):
                 raw = fp.raw_in[dst]
                 raw.copy_(input_A[src, :tG].reshape(raw.shape).to(dev, torch.float32, non_blocking=True))
 
+    def _input_table(self, in_ch):
+        """opt.input_lut as a device tensor, or the default table of in_ch channels (built once)."""
+        lut = getattr(self.opt, "input_lut", None)
+        if lut is None:
+            cache = self.__dict__.setdefault("_default_luts", {})
+            if in_ch not in cache:
+                from ..visual import input_lut
+                cache[in_ch] = input_lut(in_ch).to(self.device)
+            return cache[in_ch]
+        if not isinstance(lut, torch.Tensor) or lut.dtype != torch.float32 or tuple(lut.shape) != (in_ch, 256):
+            raise ValueError("inference: opt.input_lut is an fp32 tensor (%d, 256): one row per channel of input_A" % in_ch)
+        return lut
+
+    def _check_inputs_u8(self, input_A, restart, active):
+        """Every refusal of a call with opt.inputs_u8, before the call touches any state; returns the table of the call."""
+        opt, tG = self.opt, self.opt.n_frames_G
+        if opt.label_nc != 0:
+            raise ValueError("inference: opt.inputs_u8 is for image inputs (label_nc == 0); label maps are uint8 already")
+        if not isinstance(input_A, torch.Tensor) or input_A.dtype != torch.uint8 or input_A.dim() != 5:
+            raise ValueError("inference: with opt.inputs_u8 input_A is torch.uint8 (B, t, H, W, in_ch)")
+        B, t_in, _, _, in_ch = input_A.shape
+        if in_ch > 32:
+            raise ValueError("inference: opt.inputs_u8 decodes at most 32 input channels, input_A has %d" % in_ch)
+        if restart is not None or active is not None:
+            raise ValueError("inference: restart= / active= (slot plans) take fp32 inputs; opt.inputs_u8 runs plain plans only")
+        if B > 1 and getattr(opt, "compact_streams", False):
+            raise ValueError("inference: opt.compact_streams (pool plans) takes fp32 inputs; opt.inputs_u8 runs plain plans only")
+        running = hasattr(self, "fake_B_prev") and self.fake_B_prev is not None
+        if running and self._slots_on:
+            raise ValueError("inference: the running sequences are in a slot plan, which takes fp32 inputs")
+        if t_in not in (1, tG):
+            raise ValueError("inference: with opt.inputs_u8 input_A holds the whole window (t = %d) or the newest frame (t = 1), "
+                             "got t = %d" % (tG, t_in))
+        if t_in == 1 and tG > 1 and not (running and self._active_plan is not None and self._active_plan.win_u8 is not None):
+            raise ValueError("inference: the newest frame alone (t = 1) continues a sequence that a whole uint8 window started")
+        return self._input_table(in_ch)
+
+    def _stage_inputs_u8(self, fp, input_A, lut):
+        """uint8 inputs: the whole window, or the newest frame into slot tG - 1 of the window the plan has moved on itself."""
+        tG = self.opt.n_frames_G
+        if fp._lut_src is not lut:
+            fp.lut.copy_(lut)
+            fp._lut_src = lut
+        if input_A.shape[1] == tG:
+            fp.win_u8.copy_(input_A, non_blocking=True)
+        else:
+            fp.win_u8[:, tG - 1].copy_(input_A[:, 0], non_blocking=True)
+
     def _seed_windows(self, windows, input_A, input_B, inst_A, new=None):
         """Seed `windows` (a list per scale) from generate_first_frame: whole (new=None: the first frame of every sequence), or
         the streams in the list `new` alone, from their rows of the inputs alone (windows then have a leading stream dimension)."""
@@ -700,6 +808,8 @@ class Vid2VidModelG(BaseModel):
         if self._active_plan is not fp:
             for si in range(self.n_scales):
                 fp.prev[si].copy_(self._active_plan.prev[si])
+            if fp.win_u8 is not None and self._active_plan.win_u8 is not None:      # the uint8 input window, as far as it has moved
+                fp.win_u8.copy_(self._active_plan.win_u8)
 
     def _inference_slots(self, input_A, input_B, inst_A, act, rst, has_inst, u8, img=False):
         """One replay of the slot plan (B > 1).  act / rst: B bools.  On the first frame of the model

@@ -32,6 +32,10 @@ _DEFAULTS = dict(
     compact_streams=False,    # multi-stream inference replays a plan with one row per ACTIVE stream (stream pool)
     frames_u8=False,          # inference returns uint8 (B,H,W,3) images written by the frame plan's last launch instead of the fp32
                               # fake_B planes; an idle stream's image is zero bytes; read per call
+    inputs_u8=False,          # label_nc == 0 models: input_A is uint8 HWC (B,t,H,W,in_ch), the whole window (t = n_frames_G) on the first
+                              # call of a sequence, afterwards the newest frame alone (t = 1); decoded by the frame plan's first
+                              # launch through opt.input_lut; read per call
+    input_lut=None,           # fp32 (in_ch, 256): decoded value of every byte per channel; None = visual.input_lut(in_ch)
     ema_decay=0.0,           # training: > 0 keeps an exponential moving average of the generator's weights inside the Adam step
                               # and saves it as '<label>_net_G<s>_ema.pth' (DESIGN 3.17); 0 = off, nothing changes
     use_ema=False,            # inference: load '<epoch>_net_G<s>_ema.pth' instead of '<epoch>_net_G<s>.pth'

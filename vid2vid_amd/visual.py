@@ -90,6 +90,34 @@ def tensor2im_batch(image_tensor, normalize=True):
     return out
 
 
+def input_lut(in_ch, densepose_part_channel=None):
+    """The value table of uint8 image inputs (opt.inputs_u8): fp32 (in_ch, 256), row c the reference loader's
+    transform of every byte of channel c, by the loader's own fp32 operations in its order -- ToTensor (byte / 255) then
+    Normalize(0.5, 0.5) ((v - 0.5) / 0.5; data/base_dataset.py:148-157), and for `densepose_part_channel` (2 in the pose recipes)
+    the part-index rescale behind them, ((v * 0.5 + 0.5) * 255 / 24 - 0.5) / 0.5 (data/pose_dataset.py:44).  Nearest resize and
+    crop commute with a per-byte function, so decoding a byte through this table equals loading it through the reference."""
+    if in_ch < 1:
+        raise ValueError("input_lut: in_ch >= 1")
+    if densepose_part_channel is not None and not 0 <= densepose_part_channel < in_ch:
+        raise ValueError("input_lut: part channel %r of %d channels" % (densepose_part_channel, in_ch))
+    v = torch.arange(256, dtype=torch.uint8).to(torch.float32).div(255)
+    v = v.sub(torch.tensor(0.5)).div(torch.tensor(0.5))
+    lut = v.repeat(in_ch, 1)
+    if densepose_part_channel is not None:
+        lut[densepose_part_channel] = ((v * 0.5 + 0.5) * 255 / 24 - 0.5) / 0.5
+    return lut.contiguous()
+
+
+def decode_inputs(input_u8, lut):
+    """fp32 planes (..., C, H, W) of uint8 HWC frames (..., H, W, C) through the table `lut` (C, 256): a torch gather, for the
+    paths off the frame plan (first frames, references in tests)."""
+    C_ = input_u8.shape[-1]
+    lut = lut.to(input_u8.device)
+    planes = input_u8.movedim(-1, -3).long()                                 # (..., C, H, W)
+    idx = planes + (torch.arange(C_, device=input_u8.device) * 256).view(C_, 1, 1)
+    return lut.reshape(-1)[idx]
+
+
 def tensor2label(output, n_label):
     x = _planes(output)
     Cc, H, W = x.shape
