@@ -837,6 +837,24 @@ int v2v_tensor2im(const float* x, uint8_t* out, int32_t C, int32_t H, int32_t W,
  * NULL with K != S, out overlapping frames.  Recorded into a plan as op "frames_u8". */
 int v2v_frames_u8(const float* frames, uint8_t* out, const int32_t* mode, const int32_t* row_slot, int32_t K, int32_t S,
                   int32_t C, int32_t H, int32_t W, int32_t normalize, void* stream);
+/* The input picture of a label-model frame, straight from the label maps, in ONE launch: what v2v_tensor2label makes
+ * of the planes v2v_onehot_planar(_u8 / _batch) writes for the newest frame, without the planes.  labels and inst are
+ * [K][T][H][W], uint8 + int32 (in_u8 = 1) or fp32-encoded integers (in_u8 = 0); inst may be NULL; only frame T - 1 of every row
+ * is read.  cmap is uint8 [label_nc][3]; out is uint8 [S][H][W][3].  mode[K] / row_slot[K]: the int32 words of v2v_frames_u8,
+ * with its rules: image s comes from the first row k with row_slot[k] == s (row s without row_slot; K == S required) whose mode
+ * is 0 or 1, an image without such a row is all zero bytes, and EVERY byte of out is written by the launch.  Per pixel, with
+ * label = (int)stored value:
+ *   0 <= label < label_nc -> cmap[label];
+ *   any other label       -> black where the pixel's instance id differs from one of its 4 neighbours inside the image (the
+ *                            edge plane is the only non-zero plane and its index has no colour), cmap[0] elsewhere and without inst;
+ *   label_nc == 1 without inst (one plane: v2v_tensor2label colours the stored value) -> black for label 0, cmap[0] otherwise.
+ * The instance map is read only around pixels whose label is outside [0, label_nc).  A thread converts 16 consecutive pixels
+ * of a row (4 where W < 16) and stores them as 16-byte vectors or whole dwords; H, W and the alignment of labels / out are free.
+ * V2V_EINVAL for labels, cmap or out NULL, label_nc outside 1..255, K < 1, S < K, S > 65535, T, H or W < 1, row_slot == NULL with
+ * K != S, fp32 labels / inst / mode / row_slot not 4-byte aligned, out overlapping any input.  Recorded as op "label_image". */
+int v2v_label_image(const void* labels, const void* inst, int32_t in_u8, const uint8_t* cmap, int32_t label_nc, uint8_t* out,
+                    const int32_t* mode, const int32_t* row_slot, int32_t K, int32_t S, int32_t T, int32_t H, int32_t W,
+                    void* stream);
 /* tensor2flow (util/util.py:89-107): flow planar fp32 [2][H][W] -> uint8 [H][W][3], hue = direction / 2 degrees, value = magnitude
  * min-max normalised over the image, full saturation, HSV -> RGB as OpenCV's 8-bit conversion.  range_ws: 2 uint32 of scratch. */
 int v2v_tensor2flow(const float* flow, uint8_t* out, uint32_t* range_ws, int32_t H, int32_t W, void* stream);

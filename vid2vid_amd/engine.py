@@ -506,6 +506,7 @@ class Engine:
         self.tdtype = _TORCH_DTYPE[dtype]
         self.align_corners = align_corners
         self._packed = {}        # id(module) -> PackedConv
+        self._label_cmaps = {}   # label_nc -> uint8 (label_nc, 3) palette on the device (label_image)
         self._packed_onehot = {} # id(module) -> PackedOneHot (7x7 stems fed by label maps)
         # stems over encoded label maps as a weight gather-sum (csrc/onehot_stem.hip); V2V_ONEHOT_STEM=0: dense conv on the encoding
         self.onehot_stem = bool(int(os.environ.get("V2V_ONEHOT_STEM", "1")))
@@ -2197,6 +2198,40 @@ class Engine:
         check(lib.v2v_frames_u8(_ptr(frames), _ptr(out), _ptr(mode), _ptr(row_slot), K, S, Cc, H, W, int(bool(normalize)),
                                 _stream()), "frames_u8")
         self.label("frames_u8")
+        return out
+
+    def label_image(self, labels, inst, label_nc, slot_mode=None, row_slot=None, S=None):
+        """uint8 pictures (S, H, W, 3) of the newest frame of the label maps `labels` (K, T, H, W) -- uint8 with int32 `inst`, or
+        fp32-encoded integers with fp32 `inst`; inst may be None -- in one launch (v2v_label_image): image s is, bit
+        for bit, visual.tensor2label(onehot_planar(labels[k, T - 1], inst[k, T - 1]), label_nc) of the row k with row_slot[k] == s
+        (row s without row_slot; S = K then) whose slot_mode[k] is 0 or 1, and all zero bytes where there is none.  slot_mode /
+        row_slot: int32 (K,) device tensors read when the launch runs, or None.  The launch writes every byte of the buffer."""
+        if labels.dim() != 4 or not labels.is_contiguous() or labels.dtype not in (torch.uint8, torch.float32):
+            raise ValueError("label_image: contiguous uint8 or fp32 label maps (K, T, H, W)")
+        K, T, H, W = labels.shape
+        u8 = labels.dtype == torch.uint8
+        if inst is not None and (inst.dtype != (torch.int32 if u8 else torch.float32) or inst.shape != labels.shape
+                                 or not inst.is_contiguous()):
+            raise ValueError("label_image: the instance maps are int32 beside uint8 labels, fp32 beside fp32 ones, of their shape")
+        if not 1 <= label_nc <= 255:
+            raise ValueError("label_image: label_nc within 1..255, got %d" % label_nc)
+        S = K if S is None else int(S)
+        for t in (slot_mode, row_slot):
+            if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (K,) or not t.is_contiguous()):
+                raise ValueError("label_image: slot_mode and row_slot are int32 (K,)")
+            if t is not None:
+                self._keep(t)
+        cmap = self._label_cmaps.get(label_nc)
+        if cmap is None:
+            from .visual import labelcolormap
+            cmap = self._label_cmaps[label_nc] = torch.from_numpy(labelcolormap(label_nc)[:label_nc].copy()).to(self.device)
+        out = torch.empty((S, H, W, 3), dtype=torch.uint8, device=self.device)
+        for t in (labels, inst, cmap, out):
+            if t is not None:
+                self._keep(t)
+        check(lib.v2v_label_image(_ptr(labels), _ptr(inst), int(u8), _ptr(cmap), label_nc, _ptr(out), _ptr(slot_mode), _ptr(row_slot),
+                                  K, S, T, H, W, _stream()), "label_image")
+        self.label("label_image")
         return out
 
     def resample_flow(self, img, flow):

@@ -78,15 +78,20 @@ class _FramePlan:
     for a pool plan -- under the plan's own slot_mode / row_slot words: idle streams and slots come out as zero bytes.
     inputs_u8 (label_nc == 0, plain plans): instead of raw_in the plan owns `win_u8`, the uint8 HWC input window
     (B, tG, H, W, in_ch), and `lut`, fp32 (in_ch, 256); its first launch (Engine.image_prologue) decodes the window into the stem
-    input and real_A_last and moves it on by a frame, so a call stages the newest frame only."""
+    input and real_A_last and moves it on by a frame, so a call stages the newest frame only.
+    real_A_u8: the plan writes `out["real_A_image"]`, the uint8 input picture (B, H, W, 3) -- (S, H, W, 3) for a pool
+    plan -- under the same words as the frames.  Label plans record Engine.label_image on the label maps where real_A_last was
+    recorded, and no onehot_planar: `out["real_A_last"]` does not exist.  label_nc == 0 plans convert the first plane(s) of the
+    real_A_last they still write, by the frames_u8 launch without normalisation."""
 
     def __init__(self, model, H, W, in_ch, has_inst, use_raw_only, use_graph=True, u8=False, B=1, slots=False, pool=None,
-                 frames_u8=False, inputs_u8=False):
+                 frames_u8=False, inputs_u8=False, real_A_u8=False):
         opt, eng = model.opt, model.engine
         self.model, self.eng = model, eng
         self.H, self.W, self.use_raw_only, self.B = H, W, use_raw_only, B
         self.slots = bool(slots)
         self.frames_u8 = bool(frames_u8)
+        self.real_A_u8 = bool(real_A_u8)
         if self.slots and (B < 2 or use_raw_only):
             raise ValueError("a slot plan has B > 1 streams and decides raw-only frames per stream (slot_mode 1)")
         self.pool = pool
@@ -328,15 +333,47 @@ class _FramePlan:
         self.out["fake_B"] = fake_B
         # real_A[0][0, -1]: encoded last label frame, returned for visualisation (:209)
         if self.label_mode:      # straight from the label map: coalesced planar writes, no NHWC -> NCHW transpose
-            self.out["real_A_last"] = self._real_A_last()
+            self._emit_real_A()
         elif self.win_u8 is not None:      # the prologue decoded the newest frame into planes itself
             self.out["real_A_last"] = real_last[0] if B == 1 else real_last
         else:
             last = Act(x0.t[..., (tG - 1) * per:], per)
             last = eng.unpack(last)
             self.out["real_A_last"] = last[0] if B == 1 else last
+        self._emit_input_image()
         self._emit_image()
         self.conv_log = list(eng.conv_log)
+
+    def _emit_real_A(self):
+        """Label plans: the planar real_A_last, or with real_A_u8 the picture of it in its place (no planes are written)."""
+        if self.real_A_u8:
+            opt = self.model.opt
+            labels, inst = (self.labels, self.inst) if self.B > 1 else \
+                (self.labels.unsqueeze(0), None if self.inst is None else self.inst.unsqueeze(0))
+            if self.pool is not None:
+                self.out["real_A_image"] = self.eng.label_image(labels, inst, opt.label_nc, self.slot_mode, self.row_slot, S=self.pool.S)
+            else:
+                self.out["real_A_image"] = self.eng.label_image(labels, inst, opt.label_nc, self.slot_mode if self.slots else None)
+        else:
+            self.out["real_A_last"] = self._real_A_last()
+
+    def _emit_input_image(self):
+        """real_A_u8 plans of label_nc == 0 models: tensor2im(normalize=False) of the first c planes of real_A_last (c = 3 for
+        three input channels, else 1, as the reference's test.py picks them), by the launch of the frames."""
+        if not self.real_A_u8 or self.label_mode:
+            return
+        H, W, B = self.H, self.W, self.B
+        last = self.out["real_A_last"].view(B, -1, H, W)
+        c = 3 if last.shape[1] == 3 else 1
+        planes = last[:, :c]
+        if not planes.is_contiguous():           # several streams of more planes than the picture takes: its plane of each, densely
+            planes = self.eng.empty_f32(B, c, H, W)
+            for b in range(B):
+                self.eng.memcpy(planes[b], last[b], c * H * W * 4)
+        if self.pool is not None:
+            self.out["real_A_image"] = self.eng.frames_u8(planes, self.slot_mode, self.row_slot, S=self.pool.S, normalize=False)
+        else:
+            self.out["real_A_image"] = self.eng.frames_u8(planes, self.slot_mode if self.slots else None, normalize=False)
 
     def _real_A_last(self):
         """Planar one-hot (+ edge plane) of the newest label frame: (C, H, W), or (B, C, H, W) in one launch at B > 1."""
@@ -367,11 +404,9 @@ class _FramePlan:
             x0, mask0, prev_act, last = eng.frame_prologue(src, H, W, opt.fg_labels, opt.fg, window=prev.view(self.B, -1, H, W),
                                                            last_C=opt.output_nc)
 
-        def real_A_last():
-            self.out["real_A_last"] = self._real_A_last()
         roll = prev if rolls else None
         fake_B, flow, weight, raw, _, _, _ = netG.emit(eng, x0, prev_act, last, mask0, None, None, None, self.use_raw_only,
-                                                       tag="G0", roll=roll, side=real_A_last,
+                                                       tag="G0", roll=roll, side=self._emit_real_A,
                                                        slot_mode=self.slot_mode, row_slot=row_slot)
         if roll is None:
             self._roll(prev, fake_B)
@@ -400,6 +435,7 @@ class _FramePlan:
             self._roll(prev, fake_B)
         self.out["flow0"], self.out["weight0"], self.out["raw0"] = flow, weight, raw
         self.out["fake_B"] = fake_B
+        self._emit_input_image()
         self._emit_image()
         self.conv_log = list(eng.conv_log)
 
@@ -548,12 +584,14 @@ class Vid2VidModelG(BaseModel):
 
     # ------------------------------------------------------------------ inference
     def _frame_plan(self, H, W, in_ch, has_inst, use_raw_only, u8=False, B=1, slots=False, pool=None, frames_u8=False,
-                    inputs_u8=False):
+                    inputs_u8=False, real_A_u8=False):
         """pool: the slot capacity S of a pool plan with B rows; its key ends in ("pool", S).
         frames_u8: the plan ends in the uint8 image launch; only then its key gains a field "frames_u8".
-        inputs_u8: the plan starts with the uint8 image head; only then its key gains a last field "inputs_u8"."""
+        inputs_u8: the plan starts with the uint8 image head; only then its key gains a field "inputs_u8".
+        real_A_u8: the plan writes the uint8 input picture; only then its key gains a last field "real_A_u8"."""
         key = (H, W, in_ch, has_inst, use_raw_only, self.precision, u8, B) + (("slots",) if slots else ()) + \
-              ((("pool", pool),) if pool else ()) + (("frames_u8",) if frames_u8 else ()) + (("inputs_u8",) if inputs_u8 else ())
+              ((("pool", pool),) if pool else ()) + (("frames_u8",) if frames_u8 else ()) + (("inputs_u8",) if inputs_u8 else ()) + \
+              (("real_A_u8",) if real_A_u8 else ())
         fp = self._plans.get(key)
         if fp is None:
             self.engine.refresh_weights()
@@ -562,7 +600,7 @@ class Vid2VidModelG(BaseModel):
             saved = [w.clone() for w in windows.windows] if pool else []
             fp = _FramePlan(self, H, W, in_ch, has_inst, use_raw_only,
                             use_graph=getattr(self.opt, "use_graph", True), u8=u8, B=B, slots=slots, pool=windows,
-                            frames_u8=frames_u8, inputs_u8=inputs_u8)
+                            frames_u8=frames_u8, inputs_u8=inputs_u8, real_A_u8=real_A_u8)
             for w, keep in zip(windows.windows if pool else [], saved):
                 w.copy_(keep)
             self._plans[key] = fp
@@ -580,14 +618,16 @@ class Vid2VidModelG(BaseModel):
         `counts` (default 1..S) ahead of time: each plan records, and searches its tiles, when it is first built -- here rather
         than in the first call that happens to have that many live clips.  in_ch, has_inst, u8: as the calls will have them
         (channels of input_A, whether inst_A is given and used, uint8 label maps).  Activations cost one stream-size per row of
-        every plan built: S (S + 1) / 2 stream-sizes for all counts.  The plans are built for opt.frames_u8 as it is now."""
+        every plan built: S (S + 1) / 2 stream-sizes for all counts.  The plans are built for opt.frames_u8 and opt.real_A_u8 as
+        they are now."""
         counts = list(range(1, S + 1)) if counts is None else sorted(set(int(k) for k in counts))
         if S < 2 or not counts or counts[0] < 1 or counts[-1] > S:
             raise ValueError("prepare_streams: S >= 2 slots and active counts within 1..S")
         with torch.no_grad():
             for K in counts:
                 self._frame_plan(H, W, in_ch, bool(has_inst and self.opt.use_instance and self.opt.label_nc != 0), False, bool(u8),
-                                 B=K, pool=S, frames_u8=bool(getattr(self.opt, "frames_u8", False)))
+                                 B=K, pool=S, frames_u8=bool(getattr(self.opt, "frames_u8", False)),
+                                 real_A_u8=bool(getattr(self.opt, "real_A_u8", False)))
 
     @staticmethod
     def _slot_set(arg, B, name):
@@ -643,7 +683,15 @@ class Vid2VidModelG(BaseModel):
         opt.input_lut[c][b] (fp32 (in_ch,256); None: visual.input_lut(in_ch), the reference loader's ToTensor + Normalize); every
         result equals, bit for bit, what the call returns on those decoded fp32 planes with the option off.  Anything else --
         another t, fp32 input_A, a label model, in_ch > 32, a table of another shape, restart= / active= or opt.compact_streams
-        (slot and pool plans take fp32 inputs) -- is a ValueError that leaves the running sequences as they are."""
+        (slot and pool plans take fp32 inputs) -- is a ValueError that leaves the running sequences as they are.
+        opt.real_A_u8 (read per call): the second result is `real_A_image`, a fresh torch.uint8 tensor, instead of the
+        fp32 real_A_last.  Label models: (B,H,W,3) for every B, real_A_image[b] == visual.tensor2label(real_A_last[b], opt.label_nc)
+        bit for bit, real_A_last being what the same call returns with the option off; one launch of the frame plan writes it from
+        the label map and the instance map, and the one-hot planes are never made.  label_nc == 0: (B,H,W,c), c = 3 for three
+        input channels and 1 otherwise, real_A_image[b] == visual.tensor2im(real_A_last[b][:c], normalize=False) with its channel
+        dimension kept.  An idle stream's picture is all zero bytes.  The first result, fake_B_prev and every other state are as
+        with the option off; it combines with every option and argument above and may change between the calls of running
+        sequences."""
         opt = self.opt
         tG = opt.n_frames_G
         with torch.no_grad():
@@ -674,12 +722,15 @@ class Vid2VidModelG(BaseModel):
                                      % (B, running))
             has_inst = bool(opt.use_instance and inst_A is not None and opt.label_nc != 0)
             img = bool(getattr(opt, "frames_u8", False))
+            pic = bool(getattr(opt, "real_A_u8", False))
             if slot_call and B == 1:
                 # one stream needs no slot plan: idle is no call at all, a restart is fake_B_prev = None
                 if not act[0]:
                     last_C = in_ch if opt.label_nc == 0 else opt.label_nc + int(has_inst)
                     idle = torch.zeros(1, H, W, opt.output_nc, dtype=torch.uint8, device=self.device) if img else \
                         torch.zeros(1, opt.output_nc, H, W, dtype=torch.float32, device=self.device)
+                    if pic:
+                        return idle, torch.zeros(1, H, W, self._picture_channels(in_ch), dtype=torch.uint8, device=self.device)
                     return idle, torch.zeros(last_C, H, W, dtype=torch.float32, device=self.device)
                 if rst[0]:
                     self.fake_B_prev = None
@@ -693,13 +744,13 @@ class Vid2VidModelG(BaseModel):
             if B > 1 and getattr(opt, "compact_streams", False):
                 if not slot_call:
                     act, rst = [True] * B, [False] * B
-                return self._inference_pool(input_A, input_B, inst_A, act, rst, has_inst, u8, img)
+                return self._inference_pool(input_A, input_B, inst_A, act, rst, has_inst, u8, img, pic)
             if self._slots_on:
                 if not slot_call:
                     act, rst = [True] * B, [False] * B
-                return self._inference_slots(input_A, input_B, inst_A, act, rst, has_inst, u8, img)
+                return self._inference_slots(input_A, input_B, inst_A, act, rst, has_inst, u8, img, pic)
             use_raw_only = bool(opt.no_first_img and self.is_first_frame)
-            fp = self._frame_plan(H, W, in_ch, has_inst, use_raw_only, u8, B, frames_u8=img, inputs_u8=in_u8)
+            fp = self._frame_plan(H, W, in_ch, has_inst, use_raw_only, u8, B, frames_u8=img, inputs_u8=in_u8, real_A_u8=pic)
             if not in_u8:
                 self._stage_inputs(fp, input_A, inst_A, has_inst, list(range(B)))
             if self.is_first_frame:
@@ -716,7 +767,11 @@ class Vid2VidModelG(BaseModel):
             fp.run()
             # fresh tensors per frame, as the reference returns them (the plan's output buffers are overwritten by the
             # next replay; a caller collecting a clip must not see every entry alias the last frame)
-            return fp.out["image" if img else "fake_B"].clone(), fp.out["real_A_last"].clone()
+            return fp.out["image" if img else "fake_B"].clone(), fp.out["real_A_image" if pic else "real_A_last"].clone()
+
+    def _picture_channels(self, in_ch):
+        """Channels of real_A_image (opt.real_A_u8): the palette's 3 for label maps; for images 3 of three input channels, else 1."""
+        return 3 if self.opt.label_nc != 0 or in_ch == 3 else 1
 
     def _stage_inputs(self, fp, input_A, inst_A, has_inst, rows, in_place=False):
         """Stage (H2D or D2D) the newest tG frames of the streams `rows` (ascending) into fp's static buffers; the other streams'
@@ -811,13 +866,14 @@ class Vid2VidModelG(BaseModel):
             if fp.win_u8 is not None and self._active_plan.win_u8 is not None:      # the uint8 input window, as far as it has moved
                 fp.win_u8.copy_(self._active_plan.win_u8)
 
-    def _inference_slots(self, input_A, input_B, inst_A, act, rst, has_inst, u8, img=False):
+    def _inference_slots(self, input_A, input_B, inst_A, act, rst, has_inst, u8, img=False, pic=False):
         """One replay of the slot plan (B > 1).  act / rst: B bools.  On the first frame of the model
         (fake_B_prev = None) every active stream starts a sequence and the windows of the idle ones are zero.
-        img (opt.frames_u8): the uint8 images the plan's last launch wrote, idle rows zero, instead of fake_B."""
+        img (opt.frames_u8): the uint8 images the plan's last launch wrote, idle rows zero, instead of fake_B.
+        pic (opt.real_A_u8): the uint8 input pictures the plan wrote, idle rows zero, instead of real_A_last."""
         opt = self.opt
         B, _, in_ch, H, W = input_A.shape
-        fp = self._frame_plan(H, W, in_ch, has_inst, False, u8, B, slots=True, frames_u8=img)
+        fp = self._frame_plan(H, W, in_ch, has_inst, False, u8, B, slots=True, frames_u8=img, real_A_u8=pic)
         if self.is_first_frame:
             rst = list(act)
         # the rows of the active streams, each in its place (the buffers keep an idle stream's last valid rows)
@@ -833,18 +889,20 @@ class Vid2VidModelG(BaseModel):
         self._active_plan = fp
         self.fake_B_prev = fp.prev
         fp.run()
+        real_A = fp.out["real_A_image" if pic else "real_A_last"].clone()
         if img:                  # the image launch zeroed the idle rows itself, with or without a blend launch in front of it
-            return fp.out["image"].clone(), fp.out["real_A_last"].clone()
+            return fp.out["image"].clone(), real_A
         fake = fp.out["fake_B"].clone()
         if not fp.blend_launch and len(rows) != B:        # no blend launch in this generator: nothing wrote the idle rows' zeros
             fake[[b for b in range(B) if not act[b]]] = 0
-        return fake, fp.out["real_A_last"].clone()
+        return fake, real_A
 
-    def _inference_pool(self, input_A, input_B, inst_A, act, rst, has_inst, u8, img=False):
+    def _inference_pool(self, input_A, input_B, inst_A, act, rst, has_inst, u8, img=False, pic=False):
         """One call of a compacting model (opt.compact_streams, B = S > 1 slots): the contract of _inference_slots,
         by a replay of the pool plan that has one row per ACTIVE stream -- row k runs slot rows[k], rows ascending.
         img (opt.frames_u8): the plan's last launch delivers the (S,H,W,3) uint8 images, idle slots zero; no zero tensor and no
-        indexed copy for the frames."""
+        indexed copy for the frames.
+        pic (opt.real_A_u8): the same for the second result, the (S,H,W,3) uint8 input pictures."""
         opt, dev = self.opt, self.device
         S, _, in_ch, H, W = input_A.shape
         rows = [b for b in range(S) if act[b]]
@@ -854,14 +912,17 @@ class Vid2VidModelG(BaseModel):
             fake = torch.zeros(S, opt.output_nc, H, W, dtype=torch.float32, device=dev)
         elif K == 0:
             fake = torch.zeros(S, H, W, opt.output_nc, dtype=torch.uint8, device=dev)
-        real_A_last = torch.zeros(S, last_C, H, W, dtype=torch.float32, device=dev)
+        if not pic:
+            real_A_last = torch.zeros(S, last_C, H, W, dtype=torch.float32, device=dev)
+        elif K == 0:
+            real_A_last = torch.zeros(S, H, W, self._picture_channels(in_ch), dtype=torch.uint8, device=dev)
         if K == 0:                      # nothing is live: no replay, no state touched
             return fake, real_A_last
         pool = self._stream_pool(S, H, W)
         if not self.is_first_frame and (self._active_plan is None or self._active_plan.pool is not pool):
             raise ValueError("inference: the running sequences are not in a %d-slot pool at %dx%d; assign fake_B_prev = None "
                              "to restart" % (S, W, H))
-        fp = self._frame_plan(H, W, in_ch, has_inst, False, u8, B=K, pool=S, frames_u8=img)
+        fp = self._frame_plan(H, W, in_ch, has_inst, False, u8, B=K, pool=S, frames_u8=img, real_A_u8=pic)
         if self.is_first_frame:
             rst = list(act)
             for w in pool.windows:
@@ -879,6 +940,8 @@ class Vid2VidModelG(BaseModel):
             fake = fp.out["image"].clone()
         else:
             fake.index_copy_(0, index, fp.out["fake_B"])
+        if pic:
+            return fake, fp.out["real_A_image"].clone()
         last = fp.out["real_A_last"]
         real_A_last.index_copy_(0, index, last if K > 1 else last.unsqueeze(0))
         return fake, real_A_last

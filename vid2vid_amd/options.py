@@ -35,6 +35,9 @@ _DEFAULTS = dict(
     inputs_u8=False,          # label_nc == 0 models: input_A is uint8 HWC (B,t,H,W,in_ch), the whole window (t = n_frames_G) on the first
                               # call of a sequence, afterwards the newest frame alone (t = 1); decoded by the frame plan's first
                               # launch through opt.input_lut; read per call
+    real_A_u8=False,          # inference's second result is the uint8 input picture (B,H,W,3) -- visual.tensor2label of real_A_last, written
+                              # by one launch of the frame plan from the label map itself; tensor2im(normalize=False) of its first
+                              # plane(s) for label_nc == 0 -- instead of the fp32 planes; read per call
     input_lut=None,           # fp32 (in_ch, 256): decoded value of every byte per channel; None = visual.input_lut(in_ch)
     ema_decay=0.0,           # training: > 0 keeps an exponential moving average of the generator's weights inside the Adam step
                               # and saves it as '<label>_net_G<s>_ema.pth' (DESIGN 3.17); 0 = off, nothing changes
