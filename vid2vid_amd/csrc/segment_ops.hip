@@ -6,7 +6,9 @@
 // gather pass.  HBM-bound: feat is read twice, out written once.  First-frame path only (amortised over a sequence).
 // The float atomics make the summation ORDER run-dependent (differences at the 1e-7 level); at most
 // V2V_INSTANCE_SLOTS / 2 distinct ids per sample keep the probing short.
-// Parity on the GPU: tests/test_gpu_golden.py::test_feature_encoding_first_frame_nets_vs_reference (Encoder.forward vs the reference).
+// Parity on the GPU: tests/test_gpu_golden.py::test_feature_encoding_first_frame_nets_vs_reference (Encoder.forward vs the reference)
+// and, on the entry point itself, tests/test_gpu_small_ops.py::test_instance_mean_planar / ..._overflow (fp64 segmented mean: ids that
+// share a bucket, the table exactly full, the overflow rule of seg_assign_kernel).
 #include "v2v_internal.h"
 
 namespace v2v {
