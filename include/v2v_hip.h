@@ -781,6 +781,31 @@ int v2v_adam_step_ema(float* param, const float* grad, float* exp_avg, float* ex
 int v2v_adam_step_dev_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
                           float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                           void* state, float ema_decay, void* stream);
+/* The device-state updates behind a gradient guard (extensions like the _ema forms: nothing in the reference
+ * stands behind them).  `guard`: v2v_adam_guard_workspace_bytes() bytes, zero-initialised once and owned by the caller, 8-byte
+ * aligned, overlapping no other buffer.  It starts with
+ *     { double norm_sq; float scale; int32 skip; int32 skipped; int32 nonfinite; int32 applied; float gscale; }   (32 bytes)
+ * followed by the reduction's partials.  Three launches, ordered by the stream alone:
+ *   1. grad_sumsq: per-workgroup partials of sum grad[i]^2, every square and sum in fp64, and of the count of elements that
+ *      are not finite (<= 1024 workgroups; 16-byte loads where `grad` allows, scalar head and tail);
+ *   2. guard_finalize (one workgroup): norm_sq and nonfinite (saturating) from the partials in a fixed order -- no atomics, the
+ *      result is a pure function of grad and its alignment.  nonfinite > 0 and skip_nonfinite: skip = 1, skipped += 1, state->step
+ *      stays; otherwise skip = 0 and state->step += 1 (this launch stands in for the plain form's step increment).  Then
+ *          scale = (float)(grad_scale * min(1, max_norm / (grad_scale * sqrt(norm_sq) + 1e-6)))     (fp64, rounded once)
+ *      which is torch.nn.utils.clip_grad_norm_'s coefficient; max_norm == 0 turns clipping off and scale = grad_scale exactly,
+ *      as it is whenever the clamp is 1.  applied = state->step, gscale = grad_scale;
+ *   3. v2v_adam_step_dev / v2v_adam_step_dev_ema's update with `scale` in place of grad_scale -- the same bits as those entry
+ *      points called with grad_scale = scale -- or, with skip set, nothing: no buffer is read or written.
+ * max_norm >= 0 (not NaN).  v2v_grad_sumsq runs launches 1 and 2 alone on any buffer (max_norm 0, grad_scale 1, no skip, no
+ * state: skipped and applied keep their values). */
+int64_t v2v_adam_guard_workspace_bytes(void);
+int v2v_grad_sumsq(const float* grad, int64_t n, void* guard, void* stream);
+int v2v_adam_step_dev_guard(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                            float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                            void* state, void* guard, float max_norm, int32_t skip_nonfinite, void* stream);
+int v2v_adam_step_dev_guard_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                                float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                                void* state, float ema_decay, void* guard, float max_norm, int32_t skip_nonfinite, void* stream);
 int v2v_memset_zero(void* p, int64_t bytes, void* stream);
 
 /* ---- plan executor: a recorded launch sequence replayed as one call / one hipGraph ---- */

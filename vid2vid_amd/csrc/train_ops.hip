@@ -123,19 +123,25 @@ struct LossOp : Op {
 // ---- Adam ------------------------------------------------------------------------------
 struct AdamArgs { float* p; const float* g; float* m; float* v; long long n; float lr, b1, b2, eps, bc1, bc2_sqrt, wd, gscale; };
 
-__global__ __launch_bounds__(256) void adam_step_kernel(const AdamArgs a) {
+// The plain element loop: the one place the arithmetic of adam_step_kernel, adam_step_dev_kernel and adam_step_dev_guard_kernel
+// is written.  `gscale` is a by-value argument in the first two and the guard block's scale word in the third.
+template <typename A>
+__device__ __forceinline__ void adam_plain_elems(const A& a, float step_size, float bc2_sqrt, float gscale) {
     const long long stride = (long long)gridDim.x * blockDim.x;
-    const float step_size = a.lr / a.bc1;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) {
-        float g = a.g[i] * a.gscale;
+        float g = a.g[i] * gscale;
         const float p = a.p[i];
         if (a.wd != 0.f) g += a.wd * p;
         const float m = a.b1 * a.m[i] + (1.f - a.b1) * g;
         const float v = a.b2 * a.v[i] + (1.f - a.b2) * g * g;
         a.m[i] = m; a.v[i] = v;
-        const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
+        const float denom = sqrtf(v) / bc2_sqrt + a.eps;
         a.p[i] = p - step_size * (m / denom);
     }
+}
+
+__global__ __launch_bounds__(256) void adam_step_kernel(const AdamArgs a) {
+    adam_plain_elems(a, a.lr / a.bc1, a.bc2_sqrt, a.gscale);
 }
 
 // Graph-replayable form (optim.FusedAdam(capturable)): the 1-based step count and the learning rate live in DEVICE memory, so a
@@ -146,23 +152,15 @@ struct AdamDevArgs { float* p; const float* g; float* m; float* v; long long n; 
 
 __global__ void adam_tick_kernel(AdamDevState* st) { st->step += 1; }
 
-__global__ __launch_bounds__(256) void adam_step_dev_kernel(const AdamDevArgs a) {
-    const long long stride = (long long)gridDim.x * blockDim.x;
+__device__ __forceinline__ void adam_dev_body(const AdamDevArgs& a, float gscale) {
     const int step = a.st->step;
     const double bc1 = 1.0 - pow((double)a.b1, (double)step);        // the host form's arithmetic (v2v_adam_step), once per thread
     const double bc2 = 1.0 - pow((double)a.b2, (double)step);
-    const float step_size = a.st->lr / (float)bc1;
-    const float bc2_sqrt = (float)sqrt(bc2);
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) {
-        float g = a.g[i] * a.gscale;
-        const float p = a.p[i];
-        if (a.wd != 0.f) g += a.wd * p;
-        const float m = a.b1 * a.m[i] + (1.f - a.b1) * g;
-        const float v = a.b2 * a.v[i] + (1.f - a.b2) * g * g;
-        a.m[i] = m; a.v[i] = v;
-        const float denom = sqrtf(v) / bc2_sqrt + a.eps;
-        a.p[i] = p - step_size * (m / denom);
-    }
+    adam_plain_elems(a, a.st->lr / (float)bc1, (float)sqrt(bc2), gscale);
+}
+
+__global__ __launch_bounds__(256) void adam_step_dev_kernel(const AdamDevArgs a) {
+    adam_dev_body(a, a.gscale);
 }
 
 struct AdamDevOp : Op {
@@ -215,7 +213,7 @@ __device__ __forceinline__ void adam_ema_elem(float& p, float g, float& m, float
 }
 
 template <bool DEV>
-__global__ __launch_bounds__(256) void adam_step_ema_kernel(const AdamEmaArgs a) {
+__device__ __forceinline__ void adam_ema_body(const AdamEmaArgs& a, float gscale) {
     const long long stride = (long long)gridDim.x * blockDim.x;
     const long long t0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     AdamEmaCoef c;
@@ -230,7 +228,7 @@ __global__ __launch_bounds__(256) void adam_step_ema_kernel(const AdamEmaArgs a)
         c.bc2_sqrt = a.bc2_sqrt;
     }
     c.b1 = a.b1; c.b2 = a.b2; c.omb1 = 1.f - a.b1; c.omb2 = 1.f - a.b2;
-    c.eps = a.eps; c.wd = a.wd; c.gscale = a.gscale; c.decay = a.decay; c.omd = a.omd;
+    c.eps = a.eps; c.wd = a.wd; c.gscale = gscale; c.decay = a.decay; c.omd = a.omd;
 
     const long long vbase = a.head;
     for (long long k = t0; k < a.nvec; k += stride) {
@@ -258,6 +256,11 @@ __global__ __launch_bounds__(256) void adam_step_ema_kernel(const AdamEmaArgs a)
     }
 }
 
+template <bool DEV>
+__global__ __launch_bounds__(256) void adam_step_ema_kernel(const AdamEmaArgs a) {
+    adam_ema_body<DEV>(a, a.gscale);
+}
+
 struct AdamEmaOp : Op {
     AdamEmaArgs a; bool dev;
     int launch(hipStream_t s) override {
@@ -271,6 +274,152 @@ struct AdamEmaOp : Op {
         return check_launch();
     }
     const char* name() const override { return dev ? "adam_step_dev_ema" : "adam_step_ema"; }
+};
+
+// ---- Adam behind a gradient guard --------------------------------------------
+// Three launches ordered by the stream, no hand-off between workgroups: grad_sumsq (per-workgroup partials of sum g^2 in fp64
+// and of the count of non-finite elements) -> guard_finalize (one workgroup: fixed-order sum, the skip decision, the step word,
+// the scale) -> the device-state Adam kernels reading `scale` and `skip` from the guard block.
+struct AdamGuard {                                   // v2v_hip.h documents this layout: the host reads it back
+    double norm_sq; float scale; int skip; int skipped; int nonfinite; int applied; float gscale;
+};
+struct GuardPartial { double s; int nf; int pad; };
+enum { GUARD_MAX_BLOCKS = 1024, GUARD_HEADER_BYTES = 32 };
+static_assert(sizeof(AdamGuard) == GUARD_HEADER_BYTES && sizeof(GuardPartial) == 16, "guard block layout");
+
+__device__ __forceinline__ GuardPartial* guard_partials(AdamGuard* gd) {
+    return reinterpret_cast<GuardPartial*>(reinterpret_cast<char*>(gd) + GUARD_HEADER_BYTES);
+}
+
+struct SumsqArgs { const float* g; long long n, head, nvec; AdamGuard* gd; };
+
+__device__ __forceinline__ void sumsq_elem(float g, double& s, int& nf) {
+    const double d = (double)g;
+    s += d * d;
+    nf += isfinite(g) ? 0 : 1;
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const SumsqArgs a) {
+    __shared__ double sh[256];
+    __shared__ int shn[256];
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const long long t0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    double s = 0.0; int nf = 0;
+    const float* gv = a.g + a.head;
+    long long k = t0;
+    for (; k + 3 * stride < a.nvec; k += 4 * stride) {           // four independent 16-byte loads in flight per thread
+        const float4 g0 = *reinterpret_cast<const float4*>(gv + 4 * k);
+        const float4 g1 = *reinterpret_cast<const float4*>(gv + 4 * (k + stride));
+        const float4 g2 = *reinterpret_cast<const float4*>(gv + 4 * (k + 2 * stride));
+        const float4 g3 = *reinterpret_cast<const float4*>(gv + 4 * (k + 3 * stride));
+        sumsq_elem(g0.x, s, nf); sumsq_elem(g0.y, s, nf); sumsq_elem(g0.z, s, nf); sumsq_elem(g0.w, s, nf);
+        sumsq_elem(g1.x, s, nf); sumsq_elem(g1.y, s, nf); sumsq_elem(g1.z, s, nf); sumsq_elem(g1.w, s, nf);
+        sumsq_elem(g2.x, s, nf); sumsq_elem(g2.y, s, nf); sumsq_elem(g2.z, s, nf); sumsq_elem(g2.w, s, nf);
+        sumsq_elem(g3.x, s, nf); sumsq_elem(g3.y, s, nf); sumsq_elem(g3.z, s, nf); sumsq_elem(g3.w, s, nf);
+    }
+    for (; k < a.nvec; k += stride) {
+        const float4 g = *reinterpret_cast<const float4*>(gv + 4 * k);
+        sumsq_elem(g.x, s, nf); sumsq_elem(g.y, s, nf); sumsq_elem(g.z, s, nf); sumsq_elem(g.w, s, nf);
+    }
+    const long long nscalar = a.n - 4 * a.nvec;          // head, then the tail behind the vector part
+    for (long long j = t0; j < nscalar; j += stride) {
+        const long long i = j < a.head ? j : j + 4 * a.nvec;
+        sumsq_elem(a.g[i], s, nf);
+    }
+    sh[threadIdx.x] = s; shn[threadIdx.x] = nf;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            sh[threadIdx.x] += sh[threadIdx.x + w];
+            const long long c = (long long)shn[threadIdx.x] + shn[threadIdx.x + w];
+            shn[threadIdx.x] = c > 0x7fffffffLL ? 0x7fffffff : (int)c;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        GuardPartial* part = guard_partials(a.gd);
+        part[blockIdx.x].s = sh[0]; part[blockIdx.x].nf = shn[0];
+    }
+}
+
+struct FinalizeArgs { AdamGuard* gd; AdamDevState* st; int nblk; float gscale, max_norm; int skip_nonfinite; };
+
+__global__ __launch_bounds__(256) void guard_finalize_kernel(const FinalizeArgs a) {
+    __shared__ double sh[256];
+    __shared__ long long shn[256];
+    const GuardPartial* part = guard_partials(a.gd);
+    double s = 0.0; long long nf = 0;
+    for (int i = threadIdx.x; i < a.nblk; i += 256) { s += part[i].s; nf += part[i].nf; }
+    sh[threadIdx.x] = s; shn[threadIdx.x] = nf;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) { sh[threadIdx.x] += sh[threadIdx.x + w]; shn[threadIdx.x] += shn[threadIdx.x + w]; }
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const double norm_sq = sh[0];
+    const int bad = shn[0] > 0x7fffffffLL ? 0x7fffffff : (int)shn[0];
+    const int skip = (bad > 0 && a.skip_nonfinite) ? 1 : 0;
+    double scale = (double)a.gscale;
+    if (a.max_norm > 0.f) {                              // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max = 1)
+        double coef = (double)a.max_norm / ((double)a.gscale * sqrt(norm_sq) + 1e-6);
+        if (coef > 1.0) coef = 1.0;                      // (a NaN norm keeps its NaN, as torch's clamp does)
+        scale = (double)a.gscale * coef;
+    }
+    a.gd->norm_sq = norm_sq;
+    a.gd->scale = (float)scale;
+    a.gd->skip = skip;
+    a.gd->nonfinite = bad;
+    a.gd->gscale = a.gscale;
+    if (skip) a.gd->skipped += 1;
+    else if (a.st) a.st->step += 1;                      // stands in for adam_tick_kernel: a skipped step consumes no step number
+    if (a.st) a.gd->applied = a.st->step;
+}
+
+__global__ __launch_bounds__(256) void adam_step_dev_guard_kernel(const AdamDevArgs a, const AdamGuard* gd) {
+    if (gd->skip) return;
+    adam_dev_body(a, gd->scale);
+}
+
+__global__ __launch_bounds__(256) void adam_step_ema_guard_kernel(const AdamEmaArgs a, const AdamGuard* gd) {
+    if (gd->skip) return;
+    adam_ema_body<true>(a, gd->scale);
+}
+
+static unsigned sumsq_grid(long long n) {
+    long long b = ceil_div(n, 256 * 4);
+    if (b > GUARD_MAX_BLOCKS) b = GUARD_MAX_BLOCKS;
+    if (b < 1) b = 1;
+    return (unsigned)b;
+}
+
+struct GradSumsqOp : Op {
+    SumsqArgs a;
+    int launch(hipStream_t s) override {
+        hipLaunchKernelGGL(grad_sumsq_kernel, dim3(sumsq_grid(a.n)), dim3(256), 0, s, a);
+        return check_launch();
+    }
+    const char* name() const override { return "grad_sumsq"; }
+};
+
+struct GuardFinalizeOp : Op {
+    FinalizeArgs a;
+    int launch(hipStream_t s) override {
+        hipLaunchKernelGGL(guard_finalize_kernel, dim3(1), dim3(256), 0, s, a);
+        return check_launch();
+    }
+    const char* name() const override { return "guard_finalize"; }
+};
+
+struct AdamGuardOp : Op {
+    AdamDevArgs a; AdamEmaArgs ae; const AdamGuard* gd; bool ema;
+    int launch(hipStream_t s) override {
+        long long b = ceil_div(a.n, 256 * 4); if (b > 8192) b = 8192; if (b < 1) b = 1;
+        if (ema) hipLaunchKernelGGL(adam_step_ema_guard_kernel, dim3((unsigned)b), dim3(256), 0, s, ae, gd);
+        else     hipLaunchKernelGGL(adam_step_dev_guard_kernel, dim3((unsigned)b), dim3(256), 0, s, a, gd);
+        return check_launch();
+    }
+    const char* name() const override { return ema ? "adam_step_dev_guard_ema" : "adam_step_dev_guard"; }
 };
 
 struct MemsetOp : Op {
@@ -409,6 +558,89 @@ extern "C" int v2v_adam_step_dev_ema(float* param, const float* grad, float* exp
     op->a.b1 = beta1; op->a.b2 = beta2; op->a.eps = eps; op->a.wd = weight_decay; op->a.gscale = grad_scale;
     op->a.st = reinterpret_cast<AdamDevState*>(state);
     op->dev = true;
+    return submit(std::move(op), stream);
+}
+
+// ---- guarded forms: extensions, nothing in the reference stands behind them ----
+extern "C" int64_t v2v_adam_guard_workspace_bytes(void) { return GUARD_HEADER_BYTES + (int64_t)GUARD_MAX_BLOCKS * sizeof(GuardPartial); }
+
+// the guard block: non-null, 8-byte aligned, overlapping none of `bufs` (n floats each)
+static int guard_check(const void* guard, const void* const* bufs, int nbufs, int64_t n, const void* state = nullptr) {
+    if (!guard) { set_error("adam (guard): null guard buffer"); return V2V_EINVAL; }
+    if ((uintptr_t)guard & 7) { set_error("adam (guard): the guard buffer is not 8-byte aligned"); return V2V_EINVAL; }
+    const uintptr_t g0 = (uintptr_t)guard, gbytes = (uintptr_t)v2v_adam_guard_workspace_bytes(), bytes = (uintptr_t)n * 4;
+    for (int k = 0; k < nbufs; ++k) {
+        const uintptr_t x0 = (uintptr_t)bufs[k];
+        if (g0 < x0 + bytes && x0 < g0 + gbytes) { set_error("adam (guard): the guard buffer overlaps another buffer"); return V2V_EINVAL; }
+    }
+    const uintptr_t s0 = (uintptr_t)state;
+    if (state && g0 < s0 + sizeof(AdamDevState) && s0 < g0 + gbytes) { set_error("adam (guard): the guard buffer overlaps the state words"); return V2V_EINVAL; }
+    return 0;
+}
+
+// launches 1 and 2; `state` may be null (v2v_grad_sumsq)
+static int guard_reduce(const float* grad, int64_t n, void* guard, void* state, float grad_scale, float max_norm, int skip_nonfinite,
+                        void* stream) {
+    auto sq = std::make_unique<GradSumsqOp>();
+    memset(&sq->a, 0, sizeof(sq->a));
+    sq->a.g = grad; sq->a.n = n; sq->a.gd = reinterpret_cast<AdamGuard*>(guard);
+    const uintptr_t mis = (uintptr_t)grad & 15;
+    if ((mis & 3) == 0) {
+        sq->a.head = (long long)((16 - mis) & 15) / 4;
+        if (sq->a.head > n) sq->a.head = n;
+        sq->a.nvec = (n - sq->a.head) / 4;
+    }
+    int rc = submit(std::move(sq), stream);
+    if (rc) return rc;
+    auto fin = std::make_unique<GuardFinalizeOp>();
+    fin->a = FinalizeArgs{reinterpret_cast<AdamGuard*>(guard), reinterpret_cast<AdamDevState*>(state), (int)sumsq_grid(n),
+                          grad_scale, max_norm, skip_nonfinite ? 1 : 0};
+    return submit(std::move(fin), stream);
+}
+
+extern "C" int v2v_grad_sumsq(const float* grad, int64_t n, void* guard, void* stream) {
+    if (!grad || n <= 0) { set_error("grad_sumsq: bad argument"); return V2V_EINVAL; }
+    const void* bufs[1] = {grad};
+    int rc = guard_check(guard, bufs, 1, n);
+    if (rc) return rc;
+    return guard_reduce(grad, n, guard, nullptr, 1.f, 0.f, 0, stream);
+}
+
+extern "C" int v2v_adam_step_dev_guard(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                       float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                                       void* state, void* guard, float max_norm, int32_t skip_nonfinite, void* stream) {
+    if (!param || !grad || !exp_avg || !exp_avg_sq || n <= 0 || !state) { set_error("adam (guard): bad argument"); return V2V_EINVAL; }
+    if (!(max_norm >= 0.f)) { set_error("adam (guard): max_norm %g is negative or NaN", (double)max_norm); return V2V_EINVAL; }
+    const void* bufs[4] = {param, grad, exp_avg, exp_avg_sq};
+    int rc = guard_check(guard, bufs, 4, n, state);
+    if (rc) return rc;
+    rc = guard_reduce(grad, n, guard, state, grad_scale, max_norm, skip_nonfinite, stream);
+    if (rc) return rc;
+    auto op = std::make_unique<AdamGuardOp>();
+    op->a = AdamDevArgs{param, grad, exp_avg, exp_avg_sq, n, beta1, beta2, eps, weight_decay, grad_scale, reinterpret_cast<AdamDevState*>(state)};
+    memset(&op->ae, 0, sizeof(op->ae));
+    op->gd = reinterpret_cast<const AdamGuard*>(guard); op->ema = false;
+    return submit(std::move(op), stream);
+}
+
+extern "C" int v2v_adam_step_dev_guard_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                                           float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                                           void* state, float ema_decay, void* guard, float max_norm, int32_t skip_nonfinite,
+                                           void* stream) {
+    auto op = std::make_unique<AdamGuardOp>();
+    int rc = adam_ema_common(op->ae, param, grad, exp_avg, exp_avg_sq, ema, n, ema_decay);
+    if (rc) return rc;
+    if (!state) { set_error("adam (guard, ema): bad argument"); return V2V_EINVAL; }
+    if (!(max_norm >= 0.f)) { set_error("adam (guard, ema): max_norm %g is negative or NaN", (double)max_norm); return V2V_EINVAL; }
+    const void* bufs[5] = {param, grad, exp_avg, exp_avg_sq, ema};
+    rc = guard_check(guard, bufs, 5, n, state);
+    if (rc) return rc;
+    rc = guard_reduce(grad, n, guard, state, grad_scale, max_norm, skip_nonfinite, stream);
+    if (rc) return rc;
+    op->ae.b1 = beta1; op->ae.b2 = beta2; op->ae.eps = eps; op->ae.wd = weight_decay; op->ae.gscale = grad_scale;
+    op->ae.st = reinterpret_cast<AdamDevState*>(state);
+    memset(&op->a, 0, sizeof(op->a)); op->a.n = n;
+    op->gd = reinterpret_cast<const AdamGuard*>(guard); op->ema = true;
     return submit(std::move(op), stream);
 }
 

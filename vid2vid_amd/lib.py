@@ -124,6 +124,10 @@ PROTOTYPES = {
     "v2v_adam_step_dev": (C.c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P]),
     "v2v_adam_step_ema": (C.c_int, [_P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _I, _F, _P]),
     "v2v_adam_step_dev_ema": (C.c_int, [_P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _F, _P]),
+    "v2v_adam_guard_workspace_bytes": (_L, []),
+    "v2v_grad_sumsq": (C.c_int, [_P, _L, _P, _P]),
+    "v2v_adam_step_dev_guard": (C.c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P, _F, _I, _P]),
+    "v2v_adam_step_dev_guard_ema": (C.c_int, [_P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _F, _P, _F, _I, _P]),
     "v2v_memset_zero": (C.c_int, [_P, _L, _P]),
     "v2v_bn_finalize": (C.c_int, [_P, _I, _I, _L, _P, _P, _F, _P, _P, _P, _F, _P, _P]),
     "v2v_bn_finalize_groups": (C.c_int, [_I]),

@@ -168,6 +168,25 @@ class BaseModel(torch.nn.Module):
         print("update learning rate: %f -> %f" % (self.old_lr, lr))
         self.old_lr = lr
 
+    # ---------------- gradient guard ----------------
+    @staticmethod
+    def grad_guard_kwargs(opt):
+        """FusedAdam's guard arguments from opt.max_grad_norm / opt.skip_nonfinite_grads; empty when both are off, so that the
+        optimizers are then constructed exactly as before."""
+        max_norm = float(getattr(opt, "max_grad_norm", 0.0) or 0.0)
+        skip = bool(getattr(opt, "skip_nonfinite_grads", False))
+        return dict(max_grad_norm=max_norm, skip_nonfinite=skip) if (max_norm > 0.0 or skip) else {}
+
+    def grad_guard_stats(self):
+        """{optimizer name: FusedAdam.guard_stats()} of this model's guarded optimizers (the one train.py steps where
+        update_fixed_params left a stand-in behind `optimizer_G`); one small device-to-host read each -- for print_freq."""
+        out = {}
+        for name in sorted(k for k in vars(self) if k.startswith("optimizer_")):
+            o = getattr(self, "_" + name + "_live", None) or getattr(self, name)
+            if getattr(o, "guarded", False):
+                out[name] = o.guard_stats()
+        return out
+
     def update_fixed_params(self):
         """reference models/base_model.py:161-168, called by update_models / init_params once epoch > niter_fix_global.
 

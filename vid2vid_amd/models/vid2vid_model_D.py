@@ -82,10 +82,11 @@ class Vid2VidModelD(BaseModel):
         params = list(self.netD.parameters())
         if opt.add_face_disc:       # (reference :73-79: netD's parameters, then netD_f's)
             params += list(self.netD_f.parameters())
-        self.optimizer_D = FusedAdam(params, lr=lr, betas=(beta1, beta2))
+        guard = self.grad_guard_kwargs(opt)              # {} with opt.max_grad_norm / opt.skip_nonfinite_grads off
+        self.optimizer_D = FusedAdam(params, lr=lr, betas=(beta1, beta2), **guard)
         for s in range(opt.n_scales_temporal):
             params = list(getattr(self, "netD_T" + str(s)).parameters())
-            setattr(self, "optimizer_D_T" + str(s), FusedAdam(params, lr=opt.lr, betas=(opt.beta1, 0.999)))
+            setattr(self, "optimizer_D_T" + str(s), FusedAdam(params, lr=opt.lr, betas=(opt.beta1, 0.999), **guard))
         self.bind_precision()
 
     # ------------------------------------------------------------------ losses

@@ -560,12 +560,13 @@ class Vid2VidModelG(BaseModel):
             else:
                 beta1, beta2, lr = opt.beta1, 0.999, opt.lr
             ema_decay = float(getattr(opt, "ema_decay", 0.0) or 0.0)
+            guard = self.grad_guard_kwargs(opt)          # {} with opt.max_grad_norm / opt.skip_nonfinite_grads off
             if ema_decay > 0.0:
-                self.optimizer_G = FusedAdam(params, lr=lr, betas=(beta1, beta2), ema_decay=ema_decay)
+                self.optimizer_G = FusedAdam(params, lr=lr, betas=(beta1, beta2), ema_decay=ema_decay, **guard)
                 if opt.continue_train or opt.load_pretrain:
                     self._load_ema(opt)
             else:
-                self.optimizer_G = FusedAdam(params, lr=lr, betas=(beta1, beta2))
+                self.optimizer_G = FusedAdam(params, lr=lr, betas=(beta1, beta2), **guard)
         self.bind_precision()
 
     def _load_ema(self, opt):

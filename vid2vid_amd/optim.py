@@ -15,6 +15,7 @@ update_learning_rate (models/base_model.py:154-160) keeps working.
 """
 import ctypes as C
 import os
+import struct
 
 import torch
 
@@ -77,11 +78,15 @@ class FlatBuffers:
 
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=2e-4, betas=(0.5, 0.999), eps=1e-8, weight_decay=0.0, grad_sync=None, ema_decay=None):
+    def __init__(self, params, lr=2e-4, betas=(0.5, 0.999), eps=1e-8, weight_decay=0.0, grad_sync=None, ema_decay=None,
+                 max_grad_norm=None, skip_nonfinite=False):
         params = list(params)
         ema_decay = float(ema_decay or 0.0)
         if not 0.0 <= ema_decay <= 1.0:              # (NaN fails both comparisons)
             raise ValueError("FusedAdam: ema_decay must lie in [0, 1], got %r" % ema_decay)
+        max_grad_norm = float(max_grad_norm or 0.0)
+        if not max_grad_norm >= 0.0:
+            raise ValueError("FusedAdam: max_grad_norm must be positive (None or 0: off), got %r" % max_grad_norm)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         if len(self.param_groups) != 1:
             raise NotImplementedError("FusedAdam keeps one flat buffer: pass a single parameter list")
@@ -110,6 +115,47 @@ class FusedAdam(torch.optim.Optimizer):
         self.ema_decay = ema_decay
         if ema_decay > 0.0:
             self.ema = self.flat.flat_param.clone()
+        # gradient guard, off unless max_grad_norm > 0 or skip_nonfinite: the step becomes three launches (sum of
+        # squares of flat_grad -> decision and scale -> the device-state update reading both), all in the place of today's one,
+        # so they sit behind the all-reduce and inside a captured chunk like it.  The optimizer is then in device-state mode: a
+        # skipped step must not consume a step number and only the device knows.  With both off the object has no `_guard`
+        # attribute at all and steps through the four unguarded entry points.
+        self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = bool(skip_nonfinite)
+        if self.guarded:
+            self._guard = self._new_guard()
+            self.make_capturable()
+
+    @property
+    def guarded(self):
+        return self.max_grad_norm > 0.0 or self.skip_nonfinite
+
+    _GUARD_HEAD = struct.Struct("<dfiiiif")          # AdamGuard (include/v2v_hip.h): norm_sq, scale, skip, skipped, nonfinite, applied, gscale
+
+    def _new_guard(self, skipped=0):
+        from .lib import lib
+        words = int(lib.v2v_adam_guard_workspace_bytes()) // 4
+        host = torch.zeros(words, dtype=torch.int32)
+        host[4] = int(skipped)                       # word 4: the running count of skipped steps
+        host[6] = int(self.step_count)
+        return host.to(self.flat.flat_param.device)
+
+    def _guard_head(self):
+        """The guard block's header as a tuple, after ONE device-to-host copy (and a wait for an overlapped step)."""
+        if self.grad_sync is not None:
+            self.grad_sync.wait_pending(owner=self)
+        raw = self._guard[:self._GUARD_HEAD.size // 4].cpu().numpy().tobytes()
+        return self._GUARD_HEAD.unpack(raw)
+
+    def guard_stats(self):
+        """What the guard saw at the last step: the gradient's global L2 norm (after the all-reduce scaling), the coefficient
+        clipping multiplied it by (1.0: not clipped), the element count that was not finite (saturating), and the running
+        counts of skipped and applied updates.  The only call of the guard that synchronises with the device."""
+        if not self.guarded:
+            raise RuntimeError("FusedAdam: the gradient guard is off (max_grad_norm=None, skip_nonfinite=False)")
+        norm_sq, scale, _skip, skipped, nonfinite, applied, gscale = self._guard_head()
+        return {"grad_norm": gscale * norm_sq ** 0.5, "clip_coef": (scale / gscale) if gscale != 0.0 else 1.0,
+                "skipped": skipped, "applied": applied, "nonfinite": nonfinite}
 
     def rebuild(self, params, lr=None, betas=None):
         """Re-home a (larger) parameter list in fresh flat buffers IN PLACE: same optimizer object, same grad_sync,
@@ -139,7 +185,10 @@ class FusedAdam(torch.optim.Optimizer):
             self.flat.ready = BucketReady(self.flat, self.grad_sync)
         self.exp_avg = torch.zeros_like(self.flat.flat_param)
         self.exp_avg_sq = torch.zeros_like(self.flat.flat_param)
+        skipped = self._guard_head()[3] if self.guarded else 0
         self.step_count = 0
+        if self.guarded:
+            self._guard = self._new_guard(skipped)   # same settings, same count of skipped steps, a fresh block beside the new buffers
         if self.capturable:
             self.make_capturable()
         self.state.clear()
@@ -181,6 +230,8 @@ class FusedAdam(torch.optim.Optimizer):
         if self.ema_decay > 0.0:
             state["ema"] = self.ema.detach().cpu().clone()
             state["ema_decay"] = self.ema_decay
+        if self.guarded:
+            state["skipped"] = self._guard_head()[3]
         return state
 
     def load_state_dict(self, state):
@@ -199,6 +250,8 @@ class FusedAdam(torch.optim.Optimizer):
                     self.ema.copy_(self.flat.flat_param)     # checkpoint from a run without averaging: start from the weights
         for k, v in state.get("hyper", {}).items():
             self.param_groups[0][k] = tuple(v) if k == "betas" else v
+        if self.guarded:                             # a checkpoint of an unguarded run (or an older one) has skipped nothing
+            self._guard = self._new_guard(int(state.get("skipped", 0)))
         if self.capturable:
             self.make_capturable()                   # re-seed the device words from the restored count / learning rate
 
@@ -263,6 +316,19 @@ class FusedAdam(torch.optim.Optimizer):
             sptr = None
             if f.flat_param.is_cuda:
                 sptr = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+            if self.guarded:
+                self.sync_hyper()
+                bufs = (C.c_void_p(f.flat_param.data_ptr()), C.c_void_p(f.flat_grad.data_ptr()),
+                        C.c_void_p(self.exp_avg.data_ptr()), C.c_void_p(self.exp_avg_sq.data_ptr()))
+                hyper = (float(b1), float(b2), float(grp["eps"]), float(grp["weight_decay"]), float(gscale),
+                         C.c_void_p(self._dev_state.data_ptr()))
+                guard = (C.c_void_p(self._guard.data_ptr()), self.max_grad_norm, int(self.skip_nonfinite), sptr)
+                if self.ema_decay > 0.0:
+                    check(lib.v2v_adam_step_dev_guard_ema(*bufs, C.c_void_p(self.ema.data_ptr()), f.numel, *hyper,
+                                                          self.ema_decay, *guard), "adam_step_dev_guard_ema")
+                else:
+                    check(lib.v2v_adam_step_dev_guard(*bufs, f.numel, *hyper, *guard), "adam_step_dev_guard")
+                return
             if self.ema_decay > 0.0:
                 ema = C.c_void_p(self.ema.data_ptr())
                 if self.capturable:

@@ -42,6 +42,10 @@ _DEFAULTS = dict(
     ema_decay=0.0,           # training: > 0 keeps an exponential moving average of the generator's weights inside the Adam step
                               # and saves it as '<label>_net_G<s>_ema.pth' (DESIGN 3.17); 0 = off, nothing changes
     use_ema=False,            # inference: load '<epoch>_net_G<s>_ema.pth' instead of '<epoch>_net_G<s>.pth'
+    max_grad_norm=0.0,        # training: > 0 clips every optimizer's gradient to this global L2 norm (torch.nn.utils.clip_grad_norm_'s
+                              # rule) on the device, inside the Adam step; 0 = off, nothing changes
+    skip_nonfinite_grads=False,   # training: an optimizer step whose gradient holds an inf or a NaN is skipped -- weights, moments, the
+                              # averaged weights and the step count stay as they were; model.grad_guard_stats() reports
 )
 
 
