@@ -615,6 +615,25 @@ int v2v_frame_prologue_batch(const void* labels, const void* inst, int32_t in_u8
 int v2v_image_prologue(uint8_t* win, const float* lut, int32_t advance, void* x0, int32_t c_stride, float* real_last,
                        int32_t N, int32_t T, int32_t H, int32_t W, int32_t Cin, const float* window, int32_t win_C,
                        void* packed, int32_t win_c_stride, float* last, int32_t last_C, int32_t dtype, void* stream);
+/* The same head inside a slot plan or a pool plan: v2v_image_prologue with the frame plan's per-call words, int32 [N]
+ * in device memory, read when the launch runs (a recorded plan is replayed with other words every call).  It replaces, for
+ * label_nc == 0 models in those plans, the fp32 staging of the whole input window per call and the pack / unpack / copy launches
+ * behind it (v2v_pack_nchw_to_nhwc twice, v2v_unpack_nhwc_to_nchw, the window gather of a pool plan).
+ *   slot_mode (may be NULL)  slot_mode[n] == 2: row n is idle -- the advance is skipped, so no byte of its input window is written;
+ *              its rows of x0, real_last, packed and last are still written, from the unchanged window.  0 and 1 do not differ here.
+ *   row_slot   NULL exactly when S_win == S_window == 0.
+ *   S_win > 0     win is the pool [S_win][T][H][W][Cin]; row n stages, decodes and (on advance) moves on win[row_slot[n]], in place.
+ *   S_window > 0  window is the pool [S_window][win_C][H][W]; row n packs window[row_slot[n]] (the row_slot of
+ *              v2v_frame_prologue_pool).  S_window == 0 with S_win > 0: window is dense [N][win_C][H][W].
+ * x0, real_last, packed and last are dense [N]... in every case.  A row whose row_slot word is outside [0, S) of a pool does nothing:
+ * no pool is read or written and the row's dense outputs are left unwritten.  The words of one launch must be distinct (two rows on
+ * one slot race, inside the pool's bounds).  With NULL words and S_win == S_window == 0 this IS v2v_image_prologue.
+ * V2V_EINVAL as v2v_image_prologue, the overlap checks taken over the whole pools; for 0 < S_win < N or 0 < S_window < N, S_window > 0
+ * without window, a pool without row_slot and row_slot without a pool.  Recorded into a plan as op "image_prologue". */
+int v2v_image_prologue_slots(uint8_t* win, const float* lut, int32_t advance, void* x0, int32_t c_stride, float* real_last,
+                             int32_t N, int32_t T, int32_t H, int32_t W, int32_t Cin, const float* window, int32_t win_C,
+                             void* packed, int32_t win_c_stride, float* last, int32_t last_C, int32_t dtype, void* stream,
+                             const int32_t* slot_mode, const int32_t* row_slot, int32_t S_win, int32_t S_window);
 
 /* Stream pool (a K-row plan serving K of S slots): row_slot[K], int32 in device memory, read when the launch runs (a frame plan
  * refreshes it per replay), names the slot of the pool that dense row k works on.  The word is loaded once per row (the row is a

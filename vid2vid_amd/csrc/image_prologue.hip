@@ -18,6 +18,14 @@
 // from LDS, only bytes of the workgroup's own pixels (16-byte stores for the granules that lie inside the piece where a frame is a
 // multiple of 16 bytes, so that both frames' pieces share an alignment; single bytes at the piece's ends and otherwise), behind
 // the barrier that ends the staging: no workgroup reads a byte another one writes and goes on to use it.
+//
+// Stream slots and the stream pool (v2v_image_prologue_slots): the frame plan's per-call words, int32 [N] in device
+// memory, are loaded once per workgroup when the launch runs (blockIdx.y is the row: wave-uniform) and branched on, as
+// frame_prologue_pool_kernel loads its row_slot.  slot_mode[n] == 2 (idle) skips the advance of row n: no byte of its input
+// window is written, its dense outputs are still written from the unchanged window.  With S_win > 0 `win` is the pool
+// [S_win][T][H][W][Cin] and row n works, in place, on win[row_slot[n]]; with S_window > 0 `window` is the pool
+// [S_window][win_C][H][W] and row n packs window[row_slot[n]].  A row whose word is outside a pool returns before it reads or
+// writes anything.  Distinct words keep the ownership rule above: a workgroup writes bytes of its own pixels of its own slot.
 #include "v2v_internal.h"
 #include "layout_vec.h"
 
@@ -28,6 +36,8 @@ struct ImagePrologueArgs {
     const float* window; void* packed; float* last;
     int N, T, H, W, Cin, c_stride, win_C, win_c_stride, last_C;
     int advance, R, frame_lds;           // R: pixels per run; frame_lds: bytes of LDS per staged frame piece (multiple of 16)
+    const int* slot_mode; const int* row_slot;     // the plan's words (null: every row advances / row n is slot n)
+    int S_win, S_window;                 // > 0: win / window is a pool of that many slots, reached through row_slot
 };
 
 static constexpr int IMAGE_PROLOGUE_MAX_CIN = 32;
@@ -41,15 +51,19 @@ __global__ __launch_bounds__(256) void image_prologue_kernel(const ImagePrologue
     unsigned char* const stage = reinterpret_cast<unsigned char*>(lds_raw) + (size_t)a.Cin * 1024;   // [T][frame_lds]
     const int tid = threadIdx.x;
     const long long n = blockIdx.y;
+    const long long slot = a.row_slot ? a.row_slot[n] : n;
+    if ((a.S_win > 0 && (slot < 0 || slot >= a.S_win)) || (a.S_window > 0 && (slot < 0 || slot >= a.S_window))) return;
+    const bool advance = a.advance && !(a.slot_mode && a.slot_mode[n] == 2);
+    const long long wn = a.S_win > 0 ? slot : n;                                       // this row's input window
     const long long hw = (long long)a.H * a.W;
     const long long frame_bytes = hw * a.Cin;
-    const long long total_bytes = (long long)a.N * a.T * frame_bytes;
+    const long long total_bytes = (long long)(a.S_win > 0 ? a.S_win : a.N) * a.T * frame_bytes;
     const bool same_align = (frame_bytes & 15) == 0;
     const int vpr = a.c_stride / VEC;
     const int wvpr = a.window ? a.win_c_stride / VEC : 0;
     T* const x0 = reinterpret_cast<T*>(a.x0) + n * hw * a.c_stride;
     float* const real_last = a.real_last + n * a.Cin * hw;
-    const float* const window = a.window ? a.window + n * a.win_C * hw : nullptr;
+    const float* const window = a.window ? a.window + (a.S_window > 0 ? slot : n) * a.win_C * hw : nullptr;
     T* const packed = a.packed ? reinterpret_cast<T*>(a.packed) + n * hw * a.win_c_stride : nullptr;
     float* const last = a.last ? a.last + n * a.last_C * hw : nullptr;
 
@@ -61,7 +75,7 @@ __global__ __launch_bounds__(256) void image_prologue_kernel(const ImagePrologue
         const long long p0 = run * a.R;
         const int npix = (int)((hw - p0) < a.R ? (hw - p0) : a.R);
         const int len = npix * a.Cin;                                   // bytes of one frame's piece
-        const long long piece0 = n * a.T * frame_bytes + p0 * a.Cin;    // byte offset of frame 0's piece; frame t's: + t frame_bytes
+        const long long piece0 = wn * a.T * frame_bytes + p0 * a.Cin;    // byte offset of frame 0's piece; frame t's: + t frame_bytes
         // ---- stage: the aligned 16-byte granules that cover each frame's piece
         const int gmax = (len + 15 + 15) / 16;                          // granules of a piece at the worst alignment
         for (int i = tid; i < a.T * gmax; i += 256) {
@@ -111,7 +125,7 @@ __global__ __launch_bounds__(256) void image_prologue_kernel(const ImagePrologue
             window_pack_item<T>(window, packed, last, p0 + pix, cv, hw, a.win_C, a.win_c_stride, a.last_C);
         }
         // ---- advance: frame t's piece <- frame t + 1's, from LDS; only bytes of this run's pixels are written
-        if (a.advance) {
+        if (advance) {
             for (int t = 0; t + 1 < a.T; ++t) {
                 const long long dst0 = piece0 + t * frame_bytes;
                 const unsigned char* src = stage + (t + 1) * a.frame_lds;
@@ -162,9 +176,10 @@ static bool ranges_overlap(const void* p, long long pb, const void* q, long long
 
 using namespace v2v;
 
-extern "C" int v2v_image_prologue(uint8_t* win, const float* lut, int32_t advance, void* x0, int32_t c_stride, float* real_last,
-                                  int32_t N, int32_t T, int32_t H, int32_t W, int32_t Cin, const float* window, int32_t win_C,
-                                  void* packed, int32_t win_c_stride, float* last, int32_t last_C, int32_t dtype, void* stream) {
+extern "C" int v2v_image_prologue_slots(uint8_t* win, const float* lut, int32_t advance, void* x0, int32_t c_stride, float* real_last,
+                                        int32_t N, int32_t T, int32_t H, int32_t W, int32_t Cin, const float* window, int32_t win_C,
+                                        void* packed, int32_t win_c_stride, float* last, int32_t last_C, int32_t dtype, void* stream,
+                                        const int32_t* slot_mode, const int32_t* row_slot, int32_t S_win, int32_t S_window) {
     if (!win || !lut || !x0 || !real_last) { set_error("image_prologue: null pointer"); return V2V_EINVAL; }
     if (dtype != V2V_F32 && dtype != V2V_BF16) { set_error("image_prologue: bad dtype %d", dtype); return V2V_EINVAL; }
     const int vec = dtype == V2V_BF16 ? 8 : 4;
@@ -181,10 +196,17 @@ extern "C" int v2v_image_prologue(uint8_t* win, const float* lut, int32_t advanc
                    ((uintptr_t)window & 3) != 0 || (last && (last_C < 1 || last_C > win_C)))) {
         set_error("image_prologue: bad window pack argument"); return V2V_EINVAL;
     }
+    if (S_win < 0 || S_window < 0 || (S_win > 0 && S_win < N) || (S_window > 0 && (S_window < N || !window)) ||
+        ((S_win > 0 || S_window > 0) != (row_slot != nullptr))) {
+        set_error("image_prologue: bad pool argument (a pool of S >= N slots goes with row_slot, row_slot with a pool)"); return V2V_EINVAL;
+    }
     const long long hw = (long long)H * W;
-    const long long win_bytes = (long long)N * T * hw * Cin;
+    const long long win_bytes = (long long)(S_win > 0 ? S_win : N) * T * hw * Cin;               // the whole pool
+    const long long window_bytes = window ? (long long)(S_window > 0 ? S_window : N) * win_C * hw * 4 : 0;
     if (ranges_overlap(win, win_bytes, x0, N * hw * c_stride * esize) || ranges_overlap(win, win_bytes, real_last, N * hw * Cin * 4) ||
-        ranges_overlap(win, win_bytes, lut, Cin * 1024ll) || ranges_overlap(x0, N * hw * c_stride * esize, real_last, N * hw * Cin * 4) ||
+        ranges_overlap(win, win_bytes, lut, Cin * 1024ll) || ranges_overlap(win, win_bytes, window, window_bytes) ||
+        ranges_overlap(win, win_bytes, slot_mode, N * 4ll) || ranges_overlap(win, win_bytes, row_slot, N * 4ll) ||
+        ranges_overlap(x0, N * hw * c_stride * esize, real_last, N * hw * Cin * 4) ||
         (window && (ranges_overlap(win, win_bytes, packed, N * hw * win_c_stride * esize) ||
                     ranges_overlap(win, win_bytes, last, N * hw * (long long)last_C * 4)))) {
         set_error("image_prologue: buffers overlap"); return V2V_EINVAL;
@@ -198,7 +220,14 @@ extern "C" int v2v_image_prologue(uint8_t* win, const float* lut, int32_t advanc
     auto op = std::make_unique<ImagePrologueOp>();
     op->a = ImagePrologueArgs{win, lut, x0, real_last, window, window ? packed : nullptr, window ? last : nullptr,
                               N, T, H, W, Cin, c_stride, window ? win_C : 0, window ? win_c_stride : 0, window ? last_C : 0,
-                              advance ? 1 : 0, R, frame_lds(R)};
+                              advance ? 1 : 0, R, frame_lds(R), slot_mode, row_slot, S_win, S_window};
     op->dtype = dtype; op->lds = (unsigned)lds;
     return submit(std::move(op), stream);
+}
+
+extern "C" int v2v_image_prologue(uint8_t* win, const float* lut, int32_t advance, void* x0, int32_t c_stride, float* real_last,
+                                  int32_t N, int32_t T, int32_t H, int32_t W, int32_t Cin, const float* window, int32_t win_C,
+                                  void* packed, int32_t win_c_stride, float* last, int32_t last_C, int32_t dtype, void* stream) {
+    return v2v_image_prologue_slots(win, lut, advance, x0, c_stride, real_last, N, T, H, W, Cin, window, win_C, packed, win_c_stride,
+                                    last, last_C, dtype, stream, nullptr, nullptr, 0, 0);
 }

@@ -859,14 +859,19 @@ class Engine:
         x0 = Act(torch.empty((N, H, W, pad_channels(T * per, self.dtype)), dtype=self.tdtype, device="meta"), T * per, onehot=src)
         return x0, mask, packed, last
 
-    def image_prologue(self, win, lut, window=None, last_C=0, advance=True):
+    def image_prologue(self, win, lut, window=None, last_C=0, advance=True, slot_mode=None, row_slot=None, pooled_window=False):
         """Head of an inference frame whose inputs are 8-bit images, in one launch (v2v_image_prologue).  win: the
         input window, uint8 (N, T, H, W, Cin), oldest frame first; lut: fp32 (Cin, 256), the decoded value of every byte of every
         channel.  Returns (x0, real_last, packed Act or None, last or None): x0 the NHWC stem input, channel t * Cin + c =
         lut[c][win[n, t, y, x, c]], bit for bit Engine.pack of the decoded planes; real_last fp32 (N, Cin, H, W), the newest
         frame as x0 holds it (Engine.unpack of its channels: the decoded values, bf16-rounded in a bf16 engine); with `window`, planar fp32 (N, C, H, W), its NHWC pack and an fp32 copy of its last `last_C` planes as
         Engine.frame_prologue returns them.  advance: the launch also moves the window on by a frame, win[:, t] <- win[:, t + 1]
-        (slot T - 1 is left as it is), so the caller stages only the newest frame before the next launch."""
+        (slot T - 1 is left as it is), so the caller stages only the newest frame before the next launch.
+        slot_mode, row_slot (v2v_image_prologue_slots): int32 (N,) device tensors read by the launch when it runs.
+        slot_mode[n] == 2: row n is idle, its input window is not advanced (its outputs are written from it as it is).  row_slot:
+        `win` is then the pool (S, T, H, W, Cin), dense row n works in place on win[row_slot[n]], and the results have N =
+        row_slot.numel() rows; with pooled_window `window` is the fp32 pool (S, C, H, W) and row n packs window[row_slot[n]],
+        without it `window` is dense (N, C, H, W)."""
         if not isinstance(win, torch.Tensor) or win.dtype != torch.uint8:
             raise TypeError("image_prologue: the input window is uint8 (N, T, H, W, Cin)")
         if not isinstance(lut, torch.Tensor) or lut.dtype != torch.float32:
@@ -874,6 +879,18 @@ class Engine:
         if win.dim() != 5 or not win.is_contiguous():
             raise ValueError("image_prologue: the input window is contiguous uint8 (N, T, H, W, Cin)")
         N, T, H, W, Cin = win.shape
+        S_win = S_window = 0
+        if row_slot is not None:
+            if (not isinstance(row_slot, torch.Tensor) or row_slot.dtype != torch.int32 or row_slot.dim() != 1
+                    or not 1 <= row_slot.numel() <= N or not row_slot.is_contiguous() or row_slot.device != win.device):
+                raise ValueError("image_prologue: a pooled head reads a uint8 pool (S, T, H, W, Cin) through int32 row_slot (N,), N <= S")
+            S_win, N = N, row_slot.numel()
+        elif pooled_window:
+            raise ValueError("image_prologue: a pooled generated-frame window goes with row_slot")
+        if slot_mode is not None and (not isinstance(slot_mode, torch.Tensor) or slot_mode.dtype != torch.int32
+                                      or tuple(slot_mode.shape) != (N,) or not slot_mode.is_contiguous()
+                                      or slot_mode.device != win.device):
+            raise ValueError("image_prologue: slot_mode is int32 (%d,) on the window's device" % N)
         if Cin > 32:
             raise ValueError("image_prologue: %d input channels; the table of at most 32 channels is held in LDS" % Cin)
         if tuple(lut.shape) != (Cin, 256) or not lut.is_contiguous() or lut.device != win.device:
@@ -882,7 +899,11 @@ class Engine:
         if window is not None:
             if window.dtype != torch.float32:
                 raise TypeError("image_prologue: the generated-frame window is fp32 (N, C, H, W)")
-            if window.dim() != 4 or tuple(window.shape[::3]) != (N, W) or window.shape[2] != H or not window.is_contiguous():
+            if pooled_window:
+                if window.dim() != 4 or window.shape[0] < N or tuple(window.shape[2:]) != (H, W) or not window.is_contiguous():
+                    raise ValueError("image_prologue: %d rows at %dx%d, pooled window %s" % (N, W, H, tuple(window.shape)))
+                S_window = window.shape[0]
+            elif window.dim() != 4 or tuple(window.shape[::3]) != (N, W) or window.shape[2] != H or not window.is_contiguous():
                 raise ValueError("image_prologue: %d image streams at %dx%d, window %s" % (N, W, H, tuple(window.shape)))
             if not 0 <= last_C <= window.shape[1]:
                 raise ValueError("image_prologue: last_C = %d of a window of %d planes" % (last_C, window.shape[1]))
@@ -899,9 +920,18 @@ class Engine:
             cs = packed.Cs
             if last_C:
                 last = self.empty_f32(N, last_C, H, W)
-        check(lib.v2v_image_prologue(_ptr(win), _ptr(lut), int(bool(advance)), _ptr(x0.t), x0.Cs, _ptr(real_last), N, T, H, W, Cin,
-                                     _ptr(window), win_C, _ptr(None if packed is None else packed.t), cs, _ptr(last), last_C,
-                                     self.dtype, _stream()), "image_prologue")
+        elif pooled_window:
+            raise ValueError("image_prologue: pooled_window without a window")
+        # calls without words are the plain entry, unchanged; the slots entry takes the words and the pool sizes behind the stream
+        entry, words = "image_prologue", ()
+        if slot_mode is not None or row_slot is not None:
+            for t in (slot_mode, row_slot):
+                if t is not None:
+                    self._keep(t)
+            entry, words = "image_prologue_slots", (_ptr(slot_mode), _ptr(row_slot), S_win, S_window)
+        check(getattr(lib, "v2v_" + entry)(_ptr(win), _ptr(lut), int(bool(advance)), _ptr(x0.t), x0.Cs, _ptr(real_last), N, T, H, W,
+                                           Cin, _ptr(window), win_C, _ptr(None if packed is None else packed.t), cs, _ptr(last),
+                                           last_C, self.dtype, _stream(), *words), entry)
         self.label("image_prologue")
         return x0, real_last, packed, last
 

@@ -55,12 +55,21 @@ class _StreamPool:
     """The windows of the S stream slots of a compacting model (opt.compact_streams): fake_B_prev per scale,
     (S, tG-1, 3, h, w), owned by the model -- every pool plan of this resolution, whatever its row count K, reaches them through
     its row_slot indices, so changing K between calls copies nothing.  `idle`: the slots whose rows of the tensors the last call
-    returned are zero."""
+    returned are zero.  `inputs` (opt.inputs_u8_slots): the uint8 input windows of the slots, (S, tG, H, W, in_ch) per
+    in_ch, allocated at first use and reached through row_slot like the generated windows."""
 
     def __init__(self, S, tG, nc, H, W, n_scales, device):
         self.S, self.H, self.W = S, H, W
+        self.tG, self.device = tG, device
         self.windows = [torch.zeros(S, tG - 1, nc, H >> si, W >> si, dtype=torch.float32, device=device) for si in range(n_scales)]
+        self.inputs = {}
         self.idle = []
+
+    def input_windows(self, in_ch):
+        win = self.inputs.get(in_ch)
+        if win is None:
+            win = self.inputs[in_ch] = torch.zeros(self.S, self.tG, self.H, self.W, in_ch, dtype=torch.uint8, device=self.device)
+        return win
 
 
 class _FramePlan:
@@ -79,13 +88,16 @@ class _FramePlan:
     inputs_u8 (label_nc == 0, plain plans): instead of raw_in the plan owns `win_u8`, the uint8 HWC input window
     (B, tG, H, W, in_ch), and `lut`, fp32 (in_ch, 256); its first launch (Engine.image_prologue) decodes the window into the stem
     input and real_A_last and moves it on by a frame, so a call stages the newest frame only.
+    inputs_u8_slots: slot and pool plans take inputs_u8 too.  A slot plan owns win_u8 (B, tG, H, W, in_ch) and its head
+    runs under slot_mode (an idle stream's window is not moved on); a pool plan's `win_u8` IS the pool's input windows
+    (S, tG, H, W, in_ch), which its K rows reach through row_slot.
     real_A_u8: the plan writes `out["real_A_image"]`, the uint8 input picture (B, H, W, 3) -- (S, H, W, 3) for a pool
     plan -- under the same words as the frames.  Label plans record Engine.label_image on the label maps where real_A_last was
     recorded, and no onehot_planar: `out["real_A_last"]` does not exist.  label_nc == 0 plans convert the first plane(s) of the
     real_A_last they still write, by the frames_u8 launch without normalisation."""
 
     def __init__(self, model, H, W, in_ch, has_inst, use_raw_only, use_graph=True, u8=False, B=1, slots=False, pool=None,
-                 frames_u8=False, inputs_u8=False, real_A_u8=False):
+                 frames_u8=False, inputs_u8=False, real_A_u8=False, inputs_u8_slots=False):
         opt, eng = model.opt, model.engine
         self.model, self.eng = model, eng
         self.H, self.W, self.use_raw_only, self.B = H, W, use_raw_only, B
@@ -102,7 +114,7 @@ class _FramePlan:
         self.label_mode = opt.label_nc != 0
         dev = eng.device
         self.win_u8 = self.lut = self._lut_src = None
-        if inputs_u8 and (self.label_mode or self.slots or pool is not None):
+        if inputs_u8 and (self.label_mode or ((self.slots or pool is not None) and not inputs_u8_slots)):
             raise ValueError("uint8 image inputs (opt.inputs_u8) go with label_nc == 0 and plain plans")
         # ---- static inputs ----
         if self.label_mode:
@@ -115,7 +127,8 @@ class _FramePlan:
             self.labels = self.inst = None
             self.raw_in = None if inputs_u8 else torch.zeros(B, tG * in_ch, H, W, dtype=torch.float32, device=dev)
             if inputs_u8:
-                self.win_u8 = torch.zeros(B, tG, H, W, in_ch, dtype=torch.uint8, device=dev)
+                self.win_u8 = torch.zeros(B, tG, H, W, in_ch, dtype=torch.uint8, device=dev) if pool is None else \
+                    pool.input_windows(in_ch)
                 self.lut = torch.zeros(in_ch, 256, dtype=torch.float32, device=dev)
         # fake_B_prev[si]: (tG-1, 3, h, w) per scale, si = 0 finest  (reference :228, :248-250); (B, tG-1, 3, h, w) at B > 1
         if pool is not None:
@@ -302,7 +315,12 @@ class _FramePlan:
             # tail launches, as for label maps
             if S == 1 and not opt.fg and hasattr(m.netG0, "rolls_in_tail"):
                 return self._emit_image_head()
-            x0, real_last, _, _ = eng.image_prologue(self.win_u8, self.lut)
+            if self.slots or self.pool is not None:
+                # (idle streams of a slot plan keep their window; a pool plan's rows work on their slots of the pool's)
+                x0, real_last, _, _ = eng.image_prologue(self.win_u8, self.lut, slot_mode=self.slot_mode if self.slots else None,
+                                                         row_slot=self.row_slot)
+            else:
+                x0, real_last, _, _ = eng.image_prologue(self.win_u8, self.lut)
             mask0 = x1 = None
         else:
             x0, mask0, x1 = eng.pack(self.raw_in), None, None
@@ -420,19 +438,38 @@ class _FramePlan:
     def _emit_image_head(self):
         """The frame of a uint8-input plan at one spatial scale: image_prologue | towers ... | warp_blend.  The prologue writes
         the stem input, real_A_last, the pack of the generated-frame window and the warp's gather source, and moves the input
-        window on; the blend rolls the generated-frame window where the generator ends in it.  No pack, unpack or copy launch."""
+        window on; the blend rolls the generated-frame window where the generator ends in it.  No pack, unpack or copy launch.
+        Slot plans: the same two launches under slot_mode.  Pool plans: head and tail reach the pool's input and
+        generated windows through row_slot where the blend rolls; elsewhere the dense lowering on gathered generated windows."""
         m, eng, opt = self.model, self.eng, self.model.opt
         H, W, B = self.H, self.W, self.B
         netG = m.netG0
         prev = self.prev[0]
-        x0, real_last, prev_act, last = eng.image_prologue(self.win_u8, self.lut, window=prev.view(B, -1, H, W),
-                                                           last_C=opt.output_nc)
+        rolls = netG.rolls_in_tail(self.use_raw_only)
+        row_slot = None
+        if self.pool is not None:
+            if rolls:
+                row_slot = self.row_slot
+                window = prev.view(self.pool.S, -1, H, W)
+            else:                            # no blend launch to roll in: the dense lowering on gathered windows
+                prev = self._gathered(0)
+                window = prev.view(B, -1, H, W)
+            x0, real_last, prev_act, last = eng.image_prologue(self.win_u8, self.lut, window=window, last_C=opt.output_nc,
+                                                               row_slot=self.row_slot, pooled_window=rolls)
+        elif self.slots:
+            x0, real_last, prev_act, last = eng.image_prologue(self.win_u8, self.lut, window=prev.view(B, -1, H, W),
+                                                               last_C=opt.output_nc, slot_mode=self.slot_mode)
+        else:
+            x0, real_last, prev_act, last = eng.image_prologue(self.win_u8, self.lut, window=prev.view(B, -1, H, W),
+                                                               last_C=opt.output_nc)
         self.out["real_A_last"] = real_last[0] if B == 1 else real_last
-        roll = prev if netG.rolls_in_tail(self.use_raw_only) else None
+        roll = prev if rolls else None
         fake_B, flow, weight, raw, _, _, _ = netG.emit(eng, x0, prev_act, last, None, None, None, None, self.use_raw_only,
-                                                       tag="G0", roll=roll)
+                                                       tag="G0", roll=roll, slot_mode=self.slot_mode, row_slot=row_slot)
         if roll is None:
             self._roll(prev, fake_B)
+            if self.pool is not None:
+                eng.window_scatter(self.prev[0], prev, self.row_slot)
         self.out["flow0"], self.out["weight0"], self.out["raw0"] = flow, weight, raw
         self.out["fake_B"] = fake_B
         self._emit_input_image()
@@ -585,11 +622,12 @@ class Vid2VidModelG(BaseModel):
 
     # ------------------------------------------------------------------ inference
     def _frame_plan(self, H, W, in_ch, has_inst, use_raw_only, u8=False, B=1, slots=False, pool=None, frames_u8=False,
-                    inputs_u8=False, real_A_u8=False):
+                    inputs_u8=False, real_A_u8=False, inputs_u8_slots=False):
         """pool: the slot capacity S of a pool plan with B rows; its key ends in ("pool", S).
         frames_u8: the plan ends in the uint8 image launch; only then its key gains a field "frames_u8".
         inputs_u8: the plan starts with the uint8 image head; only then its key gains a field "inputs_u8".
-        real_A_u8: the plan writes the uint8 input picture; only then its key gains a last field "real_A_u8"."""
+        real_A_u8: the plan writes the uint8 input picture; only then its key gains a last field "real_A_u8".
+        inputs_u8_slots: a slot or pool plan may have inputs_u8; its key is told apart by the field "inputs_u8"."""
         key = (H, W, in_ch, has_inst, use_raw_only, self.precision, u8, B) + (("slots",) if slots else ()) + \
               ((("pool", pool),) if pool else ()) + (("frames_u8",) if frames_u8 else ()) + (("inputs_u8",) if inputs_u8 else ()) + \
               (("real_A_u8",) if real_A_u8 else ())
@@ -598,11 +636,14 @@ class Vid2VidModelG(BaseModel):
             self.engine.refresh_weights()
             windows = self._stream_pool(pool, H, W) if pool else None
             # building a plan replays it (warm-up, tile search): the live windows are put back behind that
-            saved = [w.clone() for w in windows.windows] if pool else []
+            live = list(windows.windows) if pool else []
+            if pool and inputs_u8:               # the uint8 input windows beside them (allocated here at first use)
+                live.append(windows.input_windows(in_ch))
+            saved = [w.clone() for w in live]
             fp = _FramePlan(self, H, W, in_ch, has_inst, use_raw_only,
                             use_graph=getattr(self.opt, "use_graph", True), u8=u8, B=B, slots=slots, pool=windows,
-                            frames_u8=frames_u8, inputs_u8=inputs_u8, real_A_u8=real_A_u8)
-            for w, keep in zip(windows.windows if pool else [], saved):
+                            frames_u8=frames_u8, inputs_u8=inputs_u8, real_A_u8=real_A_u8, inputs_u8_slots=inputs_u8_slots)
+            for w, keep in zip(live, saved):
                 w.copy_(keep)
             self._plans[key] = fp
         return fp
@@ -619,16 +660,17 @@ class Vid2VidModelG(BaseModel):
         `counts` (default 1..S) ahead of time: each plan records, and searches its tiles, when it is first built -- here rather
         than in the first call that happens to have that many live clips.  in_ch, has_inst, u8: as the calls will have them
         (channels of input_A, whether inst_A is given and used, uint8 label maps).  Activations cost one stream-size per row of
-        every plan built: S (S + 1) / 2 stream-sizes for all counts.  The plans are built for opt.frames_u8 and opt.real_A_u8 as
-        they are now."""
+        every plan built: S (S + 1) / 2 stream-sizes for all counts.  The plans are built for opt.frames_u8, opt.real_A_u8 and
+        (label_nc == 0) opt.inputs_u8 with opt.inputs_u8_slots as they are now; in_ch is then the last dimension of input_A."""
         counts = list(range(1, S + 1)) if counts is None else sorted(set(int(k) for k in counts))
         if S < 2 or not counts or counts[0] < 1 or counts[-1] > S:
             raise ValueError("prepare_streams: S >= 2 slots and active counts within 1..S")
+        in_u8 = bool(self.opt.label_nc == 0 and getattr(self.opt, "inputs_u8", False) and getattr(self.opt, "inputs_u8_slots", False))
         with torch.no_grad():
             for K in counts:
                 self._frame_plan(H, W, in_ch, bool(has_inst and self.opt.use_instance and self.opt.label_nc != 0), False, bool(u8),
-                                 B=K, pool=S, frames_u8=bool(getattr(self.opt, "frames_u8", False)),
-                                 real_A_u8=bool(getattr(self.opt, "real_A_u8", False)))
+                                 B=K, pool=S, frames_u8=bool(getattr(self.opt, "frames_u8", False)), inputs_u8=in_u8,
+                                 real_A_u8=bool(getattr(self.opt, "real_A_u8", False)), inputs_u8_slots=in_u8)
 
     @staticmethod
     def _slot_set(arg, B, name):
@@ -685,6 +727,19 @@ class Vid2VidModelG(BaseModel):
         result equals, bit for bit, what the call returns on those decoded fp32 planes with the option off.  Anything else --
         another t, fp32 input_A, a label model, in_ch > 32, a table of another shape, restart= / active= or opt.compact_streams
         (slot and pool plans take fp32 inputs) -- is a ValueError that leaves the running sequences as they are.
+        opt.inputs_u8_slots (read per call; has an effect only with opt.inputs_u8): restart=, active= and
+        opt.compact_streams are accepted with uint8 inputs.  input_A is uint8 (B,t,H,W,in_ch) with t in {1, n_frames_G}.
+        t == n_frames_G is required when the model has no running sequence or when any stream is restarted: a restarted stream
+        (on the model's first frame every active one) takes its whole window from its rows, and its first frames come from
+        visual.decode_inputs of its rows; every other active stream takes ONLY frame n_frames_G - 1 of its rows -- its older frames
+        are not read, a server need not keep them.  t == 1: each active stream takes its newest frame.  An idle stream's rows of
+        input_A are not read and its uint8 window stays bit for bit as it is; its row of fake_B / image / real_A_image is zero, its
+        row of the fp32 real_A_last is unspecified in a slot plan and zero in a pool plan, as with fp32 inputs.  The uint8 window
+        is carried plain <-> slot and pool -> slot (compact_streams cleared) with the generated windows.  A uint8 slot or pool call
+        needs no running sequence, or a running plan or pool that holds uint8 windows: a sequence fed with fp32 so far, another t,
+        restart together with t == 1 and every other refusal above are ValueErrors raised before any state is touched.  Every
+        result for every active stream equals, bit for bit, what the same call schedule returns on the same model with inputs_u8
+        off and input_A = visual.decode_inputs(...) as fp32 planes, opt.frames_u8 and opt.real_A_u8 included.
         opt.real_A_u8 (read per call): the second result is `real_A_image`, a fresh torch.uint8 tensor, instead of the
         fp32 real_A_last.  Label models: (B,H,W,3) for every B, real_A_image[b] == visual.tensor2label(real_A_last[b], opt.label_nc)
         bit for bit, real_A_last being what the same call returns with the option off; one launch of the frame plan writes it from
@@ -697,6 +752,7 @@ class Vid2VidModelG(BaseModel):
         tG = opt.n_frames_G
         with torch.no_grad():
             in_u8 = bool(getattr(opt, "inputs_u8", False))
+            lut = None
             if in_u8:
                 lut = self._check_inputs_u8(input_A, restart, active)
                 B, t_in, H, W, in_ch = input_A.shape
@@ -745,11 +801,11 @@ class Vid2VidModelG(BaseModel):
             if B > 1 and getattr(opt, "compact_streams", False):
                 if not slot_call:
                     act, rst = [True] * B, [False] * B
-                return self._inference_pool(input_A, input_B, inst_A, act, rst, has_inst, u8, img, pic)
+                return self._inference_pool(input_A, input_B, inst_A, act, rst, has_inst, u8, img, pic, lut)
             if self._slots_on:
                 if not slot_call:
                     act, rst = [True] * B, [False] * B
-                return self._inference_slots(input_A, input_B, inst_A, act, rst, has_inst, u8, img, pic)
+                return self._inference_slots(input_A, input_B, inst_A, act, rst, has_inst, u8, img, pic, lut)
             use_raw_only = bool(opt.no_first_img and self.is_first_frame)
             fp = self._frame_plan(H, W, in_ch, has_inst, use_raw_only, u8, B, frames_u8=img, inputs_u8=in_u8, real_A_u8=pic)
             if not in_u8:
@@ -817,19 +873,57 @@ class Vid2VidModelG(BaseModel):
         B, t_in, _, _, in_ch = input_A.shape
         if in_ch > 32:
             raise ValueError("inference: opt.inputs_u8 decodes at most 32 input channels, input_A has %d" % in_ch)
-        if restart is not None or active is not None:
-            raise ValueError("inference: restart= / active= (slot plans) take fp32 inputs; opt.inputs_u8 runs plain plans only")
-        if B > 1 and getattr(opt, "compact_streams", False):
-            raise ValueError("inference: opt.compact_streams (pool plans) takes fp32 inputs; opt.inputs_u8 runs plain plans only")
         running = hasattr(self, "fake_B_prev") and self.fake_B_prev is not None
-        if running and self._slots_on:
-            raise ValueError("inference: the running sequences are in a slot plan, which takes fp32 inputs")
+        if getattr(opt, "inputs_u8_slots", False):
+            self._check_inputs_u8_slots(input_A, restart, active, running)
+        else:
+            if restart is not None or active is not None:
+                raise ValueError("inference: restart= / active= (slot plans) take fp32 inputs; opt.inputs_u8 runs plain plans only")
+            if B > 1 and getattr(opt, "compact_streams", False):
+                raise ValueError("inference: opt.compact_streams (pool plans) takes fp32 inputs; opt.inputs_u8 runs plain plans only")
+            if running and self._slots_on:
+                raise ValueError("inference: the running sequences are in a slot plan, which takes fp32 inputs")
         if t_in not in (1, tG):
             raise ValueError("inference: with opt.inputs_u8 input_A holds the whole window (t = %d) or the newest frame (t = 1), "
                              "got t = %d" % (tG, t_in))
         if t_in == 1 and tG > 1 and not (running and self._active_plan is not None and self._active_plan.win_u8 is not None):
             raise ValueError("inference: the newest frame alone (t = 1) continues a sequence that a whole uint8 window started")
         return self._input_table(in_ch)
+
+    def _check_inputs_u8_slots(self, input_A, restart, active, running):
+        """opt.inputs_u8_slots: what a uint8 call with restart= / active= / opt.compact_streams, or one that continues
+        a slot plan, needs beyond _check_inputs_u8's rules -- checked, like them, before the call touches any state."""
+        opt, tG = self.opt, self.opt.n_frames_G
+        B, t_in = input_A.shape[:2]
+        rst = restart is not None and any(self._slot_set(restart, B, "restart"))
+        if rst and t_in != tG:
+            raise ValueError("inference: a restarted stream takes its whole uint8 window (t = %d), got t = %d" % (tG, t_in))
+        slot_call = B > 1 and (restart is not None or active is not None or bool(getattr(opt, "compact_streams", False))
+                               or (running and self._slots_on))
+        if slot_call and running and (self._active_plan is None or self._active_plan.win_u8 is None):
+            raise ValueError("inference: the running sequences were fed fp32 inputs; a uint8 slot or pool call continues uint8 "
+                             "windows (assign fake_B_prev = None to restart)")
+
+    def _stage_inputs_u8_slots(self, fp, input_A, lut, rows, new):
+        """uint8 inputs of a slot or pool plan: stream b's window is fp.win_u8[b] (the slot plan's own, or the pool's).  The
+        streams in `new` take their whole window from their rows; every other stream of `rows` (the active ones, ascending) takes
+        the newest frame of its rows alone, into slot tG - 1 of the window the plan has moved on.  One copy when every stream is
+        active (_stage_inputs' rule), else one per active row; the idle streams' rows are not read."""
+        tG, win = self.opt.n_frames_G, fp.win_u8
+        if fp._lut_src is not lut:
+            fp.lut.copy_(lut)
+            fp._lut_src = lut
+        if len(rows) == win.shape[0]:
+            if len(new) == len(rows):
+                win.copy_(input_A, non_blocking=True)
+                return
+            win[:, tG - 1].copy_(input_A[:, -1], non_blocking=True)
+        else:
+            for b in rows:
+                if b not in new:
+                    win[b, tG - 1].copy_(input_A[b, -1], non_blocking=True)
+        for b in new:
+            win[b].copy_(input_A[b], non_blocking=True)
 
     def _stage_inputs_u8(self, fp, input_A, lut):
         """uint8 inputs: the whole window, or the newest frame into slot tG - 1 of the window the plan has moved on itself."""
@@ -842,13 +936,18 @@ class Vid2VidModelG(BaseModel):
         else:
             fp.win_u8[:, tG - 1].copy_(input_A[:, 0], non_blocking=True)
 
-    def _seed_windows(self, windows, input_A, input_B, inst_A, new=None):
+    def _seed_windows(self, windows, input_A, input_B, inst_A, new=None, lut=None):
         """Seed `windows` (a list per scale) from generate_first_frame: whole (new=None: the first frame of every sequence), or
-        the streams in the list `new` alone, from their rows of the inputs alone (windows then have a leading stream dimension)."""
+        the streams in the list `new` alone, from their rows of the inputs alone (windows then have a leading stream dimension).
+        lut: input_A is uint8 HWC and the first-frame generators get visual.decode_inputs of the rows they read."""
         if new is None:
             first = self.generate_first_frame(input_A, input_B, inst_A)         # list per scale (tG-1,3,h,w) / (B,tG-1,3,h,w)
         elif new:
-            first = self.generate_first_frame(input_A[new], None if input_B is None else input_B[new],
+            rows_A = input_A[new]
+            if lut is not None:
+                from ..visual import decode_inputs
+                rows_A = decode_inputs(rows_A.to(self.device), lut)
+            first = self.generate_first_frame(rows_A, None if input_B is None else input_B[new],
                                               None if inst_A is None else inst_A[new])
         else:
             return
@@ -867,25 +966,37 @@ class Vid2VidModelG(BaseModel):
             if fp.win_u8 is not None and self._active_plan.win_u8 is not None:      # the uint8 input window, as far as it has moved
                 fp.win_u8.copy_(self._active_plan.win_u8)
 
-    def _inference_slots(self, input_A, input_B, inst_A, act, rst, has_inst, u8, img=False, pic=False):
+    def _inference_slots(self, input_A, input_B, inst_A, act, rst, has_inst, u8, img=False, pic=False, lut=None):
         """One replay of the slot plan (B > 1).  act / rst: B bools.  On the first frame of the model
         (fake_B_prev = None) every active stream starts a sequence and the windows of the idle ones are zero.
         img (opt.frames_u8): the uint8 images the plan's last launch wrote, idle rows zero, instead of fake_B.
-        pic (opt.real_A_u8): the uint8 input pictures the plan wrote, idle rows zero, instead of real_A_last."""
+        pic (opt.real_A_u8): the uint8 input pictures the plan wrote, idle rows zero, instead of real_A_last.
+        lut (opt.inputs_u8 with opt.inputs_u8_slots): input_A is uint8 (B,t,H,W,in_ch) and this is the call's table."""
         opt = self.opt
-        B, _, in_ch, H, W = input_A.shape
-        fp = self._frame_plan(H, W, in_ch, has_inst, False, u8, B, slots=True, frames_u8=img, real_A_u8=pic)
+        in_u8 = lut is not None
+        if in_u8:
+            B, _, H, W, in_ch = input_A.shape
+        else:
+            B, _, in_ch, H, W = input_A.shape
+        fp = self._frame_plan(H, W, in_ch, has_inst, False, u8, B, slots=True, frames_u8=img, inputs_u8=in_u8, real_A_u8=pic,
+                              inputs_u8_slots=in_u8)
         if self.is_first_frame:
             rst = list(act)
         # the rows of the active streams, each in its place (the buffers keep an idle stream's last valid rows)
         rows = [b for b in range(B) if act[b]]
-        self._stage_inputs(fp, input_A, inst_A, has_inst, rows, in_place=True)
+        new = [b for b in range(B) if rst[b]]
+        if not in_u8:
+            self._stage_inputs(fp, input_A, inst_A, has_inst, rows, in_place=True)
         if self.is_first_frame:
             for si in range(self.n_scales):
                 fp.prev[si].zero_()
+            if in_u8:
+                fp.win_u8.zero_()
         else:
             self._carry_windows(fp)                                              # plain plan -> slot plan
-        self._seed_windows(fp.prev, input_A, input_B, inst_A, [b for b in range(B) if rst[b]])
+        self._seed_windows(fp.prev, input_A, input_B, inst_A, new, lut)
+        if in_u8:                        # behind the carry: into the windows the sequences have reached
+            self._stage_inputs_u8_slots(fp, input_A, lut, rows, new)
         fp.set_words([2 if not act[b] else (1 if (rst[b] and opt.no_first_img) else 0) for b in range(B)])
         self._active_plan = fp
         self.fake_B_prev = fp.prev
@@ -898,14 +1009,20 @@ class Vid2VidModelG(BaseModel):
             fake[[b for b in range(B) if not act[b]]] = 0
         return fake, real_A
 
-    def _inference_pool(self, input_A, input_B, inst_A, act, rst, has_inst, u8, img=False, pic=False):
+    def _inference_pool(self, input_A, input_B, inst_A, act, rst, has_inst, u8, img=False, pic=False, lut=None):
         """One call of a compacting model (opt.compact_streams, B = S > 1 slots): the contract of _inference_slots,
         by a replay of the pool plan that has one row per ACTIVE stream -- row k runs slot rows[k], rows ascending.
         img (opt.frames_u8): the plan's last launch delivers the (S,H,W,3) uint8 images, idle slots zero; no zero tensor and no
         indexed copy for the frames.
-        pic (opt.real_A_u8): the same for the second result, the (S,H,W,3) uint8 input pictures."""
+        pic (opt.real_A_u8): the same for the second result, the (S,H,W,3) uint8 input pictures.
+        lut (opt.inputs_u8 with opt.inputs_u8_slots): input_A is uint8 (S,t,H,W,in_ch), staged into the pool's uint8
+        input windows, slot b's rows into window b; the plan's rows reach them through row_slot."""
         opt, dev = self.opt, self.device
-        S, _, in_ch, H, W = input_A.shape
+        in_u8 = lut is not None
+        if in_u8:
+            S, _, H, W, in_ch = input_A.shape
+        else:
+            S, _, in_ch, H, W = input_A.shape
         rows = [b for b in range(S) if act[b]]
         K = len(rows)
         last_C = in_ch if opt.label_nc == 0 else opt.label_nc + int(has_inst)
@@ -923,13 +1040,20 @@ class Vid2VidModelG(BaseModel):
         if not self.is_first_frame and (self._active_plan is None or self._active_plan.pool is not pool):
             raise ValueError("inference: the running sequences are not in a %d-slot pool at %dx%d; assign fake_B_prev = None "
                              "to restart" % (S, W, H))
-        fp = self._frame_plan(H, W, in_ch, has_inst, False, u8, B=K, pool=S, frames_u8=img, real_A_u8=pic)
+        fp = self._frame_plan(H, W, in_ch, has_inst, False, u8, B=K, pool=S, frames_u8=img, inputs_u8=in_u8, real_A_u8=pic,
+                              inputs_u8_slots=in_u8)
         if self.is_first_frame:
             rst = list(act)
             for w in pool.windows:
                 w.zero_()
-        self._stage_inputs(fp, input_A, inst_A, has_inst, rows)           # the active streams' rows, straight into the dense rows
-        self._seed_windows(pool.windows, input_A, input_B, inst_A, [b for b in range(S) if rst[b]])
+            if in_u8:
+                fp.win_u8.zero_()
+        new = [b for b in range(S) if rst[b]]
+        if in_u8:
+            self._stage_inputs_u8_slots(fp, input_A, lut, rows, new)      # the active streams' rows, each into its slot's window
+        else:
+            self._stage_inputs(fp, input_A, inst_A, has_inst, rows)       # the active streams' rows, straight into the dense rows
+        self._seed_windows(pool.windows, input_A, input_B, inst_A, new, lut)
         fp.set_words(rows + [1 if (rst[b] and opt.no_first_img) else 0 for b in rows])
         pool.idle = [b for b in range(S) if not act[b]]
         self._active_plan = fp

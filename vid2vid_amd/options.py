@@ -35,6 +35,8 @@ _DEFAULTS = dict(
     inputs_u8=False,          # label_nc == 0 models: input_A is uint8 HWC (B,t,H,W,in_ch), the whole window (t = n_frames_G) on the first
                               # call of a sequence, afterwards the newest frame alone (t = 1); decoded by the frame plan's first
                               # launch through opt.input_lut; read per call
+    inputs_u8_slots=False,    # with inputs_u8: restart= / active= and compact_streams take uint8 inputs too -- the slot plan and the
+                              # stream pool own uint8 input windows, decoded under the plan's words; read per call
     real_A_u8=False,          # inference's second result is the uint8 input picture (B,H,W,3) -- visual.tensor2label of real_A_last, written
                               # by one launch of the frame plan from the label map itself; tensor2im(normalize=False) of its first
                               # plane(s) for label_nc == 0 -- instead of the fp32 planes; read per call
