@@ -635,6 +635,28 @@ int v2v_image_prologue_slots(uint8_t* win, const float* lut, int32_t advance, vo
                              void* packed, int32_t win_c_stride, float* last, int32_t last_C, int32_t dtype, void* stream,
                              const int32_t* slot_mode, const int32_t* row_slot, int32_t S_win, int32_t S_window);
 
+/* uint8 frames at SOURCE size into uint8 frames at model size -- the input windows of v2v_image_prologue -- in ONE launch (DESIGN
+ * 3.24): the loaders' nearest resize, crop and flip (data/base_dataset.py:130-175 under the parameters of get_img_params :85-128,
+ * with method = Image.NEAREST as the pose and face datasets pass for their input maps) as one integer index map per frame.
+ *   src      uint8 [F][Hs][Ws][C], read only;   dst  uint8 [D][H][W][C]
+ *   entries  int32 [E][4] = {src_frame, dst_frame, geom, 0}: dst[dst_frame] <- src[src_frame] under geoms[geom]
+ *   geoms    int32 [G][8] = {new_w, new_h, x1, y1, flip, 0, 0, 0}: the frame is resized to new_w x new_h, the H x W box at (x1, y1)
+ *            of that is kept (x1 = y1 = 0, W = new_w, H = new_h without a crop) and mirrored left-right where flip != 0
+ * Destination pixel (y, x) is source pixel (src_y, src_x):
+ *   x' = flip ? W - 1 - x : x;  src_x = ((2 (x' + x1) + 1) Ws) / (2 new_w);   src_y = ((2 (y + y1) + 1) Hs) / (2 new_h)
+ * in integers -- Pillow's resize(NEAREST) followed by crop and transpose(FLIP_LEFT_RIGHT), byte for byte.  Both tables are in
+ * device memory (16-byte aligned) and are read when the launch runs, so a recorded launch serves other frames and geometries on
+ * its next replay.  An entry whose src_frame, dst_frame or geom is outside [0, F), [0, D), [0, G) does nothing, and so does one
+ * whose geometry does not hold the box (x1 < 0, y1 < 0, x1 + W > new_w, y1 + H > new_h, new_w or new_h outside 1..16384): no
+ * source index leaves [0, Hs) x [0, Ws).  Entries of one launch name distinct dst frames (two on one frame race, inside the
+ * frame); frames that no entry names are not written.  Rows leave as 16-byte stores where the row's bytes allow, a pixel's bytes
+ * are loaded as dwords where C is a multiple of 4 and src and dst are 4-byte aligned; no alignment is required of src or dst.
+ * V2V_EINVAL for a null src / dst / entries / geoms, C outside 1..32, Hs, Ws, H or W outside 1..16384 (which keeps the index
+ * arithmetic inside int32), F, D or G < 1, E outside 0..65535, tables that are not 16-byte aligned, dst overlapping src or a
+ * table.  E == 0 launches nothing.  Recorded into a plan as op "gather_frames_u8". */
+int v2v_gather_frames_u8(const uint8_t* src, int32_t F, int32_t Hs, int32_t Ws, uint8_t* dst, int32_t D, int32_t H, int32_t W,
+                         int32_t C, const int32_t* entries, int32_t E, const int32_t* geoms, int32_t G, void* stream);
+
 /* Stream pool (a K-row plan serving K of S slots): row_slot[K], int32 in device memory, read when the launch runs (a frame plan
  * refreshes it per replay), names the slot of the pool that dense row k works on.  The word is loaded once per row (the row is a
  * grid dimension) and branched on.  A row whose word is outside [0, S) does nothing: no window is read or written and the row's

@@ -935,6 +935,38 @@ class Engine:
         self.label("image_prologue")
         return x0, real_last, packed, last
 
+    def gather_frames_u8(self, src, dst, entries, geoms):
+        """uint8 frames at source size into uint8 frames at model size in one launch (v2v_gather_frames_u8): the
+        loaders' nearest resize, crop and flip as an integer index map.  src: contiguous uint8 (..., Hs, Ws, C), its leading
+        dimensions taken together as F frames; dst: contiguous uint8 (..., H, W, C), D frames -- e.g. a plan's or the pool's
+        input windows (B, T, H, W, C).  entries: int32 (E, 4) = [src_frame, dst_frame, geom, 0]; geoms: int32 (G, 8) =
+        [new_w, new_h, x1, y1, flip, 0, 0, 0] (visual.geometry_words); both in device memory, read when the launch runs, so
+        inside a recorded plan (op "gather_frames_u8") a replay serves whatever the tables then hold.  Frames that no entry names
+        are not written; an entry out of range does nothing.  E == 0 launches nothing."""
+        for t, what in ((src, "src"), (dst, "dst")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+                raise TypeError("gather_frames_u8: %s is uint8 (..., rows, columns, C)" % what)
+            if t.dim() < 3 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError("gather_frames_u8: %s is contiguous uint8 (..., rows, columns, C) on the engine's device" % what)
+        for t, what, cols in ((entries, "entries", 4), (geoms, "geoms", 8)):
+            if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != cols
+                    or not t.is_contiguous() or t.device != self.device or t.data_ptr() % 16 != 0):
+                raise ValueError("gather_frames_u8: %s is contiguous int32 (n, %d) on the engine's device, 16-byte aligned" % (what, cols))
+        Hs, Ws, Cc = src.shape[-3:]
+        H, W = dst.shape[-3:-1]
+        if dst.shape[-1] != Cc or not 1 <= Cc <= 32:
+            raise ValueError("gather_frames_u8: src and dst have the same 1..32 channels, got %d and %d" % (Cc, dst.shape[-1]))
+        if max(Hs, Ws, H, W) > 16384 or min(Hs, Ws, H, W) < 1 or geoms.shape[0] < 1 or entries.shape[0] > 65535:
+            raise ValueError("gather_frames_u8: frames of 1..16384 rows and columns, at least one geometry, at most 65535 entries")
+        if entries.shape[0] == 0:
+            return
+        F, D = src.numel() // (Hs * Ws * Cc), dst.numel() // (H * W * Cc)
+        for t in (src, dst, entries, geoms):
+            self._keep(t)
+        check(lib.v2v_gather_frames_u8(_ptr(src), F, Hs, Ws, _ptr(dst), D, H, W, Cc, _ptr(entries), entries.shape[0],
+                                       _ptr(geoms), geoms.shape[0], _stream()), "gather_frames_u8")
+        self.label("gather_frames_u8")
+
     def onehot_conv(self, x, conv, want_stats=True, label="", fin=None):
         """Raw fp32 NHWC output + statistics rows of the stem convolution, computed from the label maps behind `x`.
         Returns (raw, rows, (N, OH, OW)) like conv(..., OUT_RAW_F32_NHWC, want_stats=True).  fin = (norm, ss): the

@@ -184,6 +184,7 @@ PROTOTYPES = {
     "v2v_image_prologue": (C.c_int, [_P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P]),
     "v2v_image_prologue_slots": (C.c_int, [_P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P,
                                            _P, _P, _I, _I]),
+    "v2v_gather_frames_u8": (C.c_int, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P]),
     "v2v_warp_blend_pool": (C.c_int, [_P] * 11 + [_I] + [_P, _P] + [_I] * 6 + [_P]),
     "v2v_window_gather_pool": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "v2v_window_scatter_pool": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),

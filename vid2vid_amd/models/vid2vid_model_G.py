@@ -138,6 +138,7 @@ class _FramePlan:
                          for si in range(S)]
         # the plan's int32 words, refreshed per call by set_words: slot_mode (B,) of a slot plan, row_slot | row_mode of a pool plan
         self.slot_mode = self.row_slot = self._words = self._words_host = self._words_copied = None
+        self._gather = None              # [pinned host tables, device tables, copy event] of opt.input_geometry calls, at first use
         if self.slots:
             self.slot_mode = self._words = torch.zeros(B, dtype=torch.int32, device=dev)
             # does the finest generator end in the blend launch (which writes an idle stream's row of zeros)?
@@ -531,6 +532,30 @@ class _FramePlan:
             self._words_copied = torch.cuda.Event()
             self._words_copied.record()
 
+    def gather_tables(self, entries, geoms):
+        """The tables of a call's gather launch (opt.input_geometry) in device memory: (entries int32 (E, 4), geoms
+        int32 (G, 8)), views of one buffer sized for every frame of the uint8 windows and a geometry per stream.  Like the plan's
+        words they are written into pinned host memory and cross by one asynchronous copy; the host buffer is rewritten only after
+        the previous copy out of it has completed."""
+        streams, frames = self.win_u8.shape[0], self.win_u8.shape[0] * self.win_u8.shape[1]
+        if self._gather is None:
+            host = torch.zeros(4 * frames + 8 * streams, dtype=torch.int32)
+            if self.win_u8.device.type == "cuda":
+                host = host.pin_memory()
+            self._gather = [host, torch.zeros(host.numel(), dtype=torch.int32, device=self.win_u8.device), None]
+        host, dev, copied = self._gather
+        if copied is not None:
+            copied.synchronize()
+        E, G = len(entries), len(geoms)
+        host[:4 * E].copy_(torch.tensor(entries, dtype=torch.int32).reshape(-1))
+        host[4 * frames:4 * frames + 8 * G].copy_(torch.tensor(geoms, dtype=torch.int32).reshape(-1))
+        dev.copy_(host, non_blocking=True)
+        if dev.device.type == "cuda":
+            self._gather[2] = torch.cuda.Event()
+            self._gather[2].record()
+        self.gather_last = (dev[:4 * E].view(E, 4), dev[4 * frames:4 * frames + 8 * G].view(G, 8))     # (tests read them)
+        return self.gather_last
+
     def run(self):
         if self.eng.record_only:
             return            # CPU dry run: the plan was validated and recorded, nothing can execute
@@ -740,6 +765,16 @@ class Vid2VidModelG(BaseModel):
         restart together with t == 1 and every other refusal above are ValueErrors raised before any state is touched.  Every
         result for every active stream equals, bit for bit, what the same call schedule returns on the same model with inputs_u8
         off and input_A = visual.decode_inputs(...) as fp32 planes, opt.frames_u8 and opt.real_A_u8 included.
+        opt.input_geometry (read per call; with opt.inputs_u8, and opt.inputs_u8_slots for slot and pool calls): input_A
+        is uint8 (B,t,Hs,Ws,in_ch) at SOURCE size, on host or device, and the option is the reference's get_img_params dict
+        (new_size, crop_size, crop_pos, flip) or a list of B of them, one per stream.  One launch in front of the frame plan writes
+        what the reference loader's img.resize(new_size, Image.NEAREST), __crop and flip make of every frame the call brings into
+        the plan's uint8 windows -- t = n_frames_G frames of a started or restarted stream, the newest frame of every other active
+        one, nothing of an idle one; the rules for t are those above.  (H, W) of the call is visual.geometry_size of the
+        geometries, which must agree with each other and with the running sequences.  Every result equals, bit for bit, the same
+        call with the option off on frames resized that way on the host.  The option without opt.inputs_u8 or on a label model, a
+        list of another length, sizes that differ, new_size or source sizes outside 1..16384, a crop_pos outside the resized frame
+        and a flip that is no bool are ValueErrors raised before anything is staged or launched.
         opt.real_A_u8 (read per call): the second result is `real_A_image`, a fresh torch.uint8 tensor, instead of the
         fp32 real_A_last.  Label models: (B,H,W,3) for every B, real_A_image[b] == visual.tensor2label(real_A_last[b], opt.label_nc)
         bit for bit, real_A_last being what the same call returns with the option off; one launch of the frame plan writes it from
@@ -752,10 +787,16 @@ class Vid2VidModelG(BaseModel):
         tG = opt.n_frames_G
         with torch.no_grad():
             in_u8 = bool(getattr(opt, "inputs_u8", False))
-            lut = None
+            lut = geo = None
+            if getattr(opt, "input_geometry", None) is not None and (not in_u8 or opt.label_nc != 0):
+                raise ValueError("inference: opt.input_geometry goes with opt.inputs_u8 on an image model (label_nc == 0); "
+                                 "visual.resample_u8 resizes label maps")
             if in_u8:
                 lut = self._check_inputs_u8(input_A, restart, active)
+                geo = self._check_input_geometry(input_A)
                 B, t_in, H, W, in_ch = input_A.shape
+                if geo is not None:                  # input_A is at source size; the model's size is the geometry's
+                    H, W = geo[:2]
             else:
                 B, t_in, in_ch, H, W = input_A.shape
                 if t_in < tG:
@@ -801,11 +842,11 @@ class Vid2VidModelG(BaseModel):
             if B > 1 and getattr(opt, "compact_streams", False):
                 if not slot_call:
                     act, rst = [True] * B, [False] * B
-                return self._inference_pool(input_A, input_B, inst_A, act, rst, has_inst, u8, img, pic, lut)
+                return self._inference_pool(input_A, input_B, inst_A, act, rst, has_inst, u8, img, pic, lut, geo)
             if self._slots_on:
                 if not slot_call:
                     act, rst = [True] * B, [False] * B
-                return self._inference_slots(input_A, input_B, inst_A, act, rst, has_inst, u8, img, pic, lut)
+                return self._inference_slots(input_A, input_B, inst_A, act, rst, has_inst, u8, img, pic, lut, geo)
             use_raw_only = bool(opt.no_first_img and self.is_first_frame)
             fp = self._frame_plan(H, W, in_ch, has_inst, use_raw_only, u8, B, frames_u8=img, inputs_u8=in_u8, real_A_u8=pic)
             if not in_u8:
@@ -813,11 +854,18 @@ class Vid2VidModelG(BaseModel):
             if self.is_first_frame:
                 # (uint8 inputs: the first-frame generators read fp32 planes -- decoded once per sequence, off the hot path)
                 from ..visual import decode_inputs
-                planes = decode_inputs(input_A.to(self.device), lut) if in_u8 else input_A
+                if geo is not None:      # ... of the frames at model size: the gather launch goes first and they read its window
+                    self._stage_inputs_geometry(fp, input_A, lut, list(range(B)), list(range(B)), geo)
+                    planes = decode_inputs(fp.win_u8, lut)
+                else:
+                    planes = decode_inputs(input_A.to(self.device), lut) if in_u8 else input_A
                 self._seed_windows(fp.prev, planes, input_B, inst_A)
             else:
                 self._carry_windows(fp)                                          # e.g. first-frame plan -> steady plan
-            if in_u8:                    # behind the carry: the newest frame lands in the window the sequence has reached
+            if geo is not None:
+                if not self.is_first_frame:
+                    self._stage_inputs_geometry(fp, input_A, lut, list(range(B)), list(range(B)) if t_in == tG else [], geo)
+            elif in_u8:                  # behind the carry: the newest frame lands in the window the sequence has reached
                 self._stage_inputs_u8(fp, input_A, lut)
             self._active_plan = fp
             self.fake_B_prev = fp.prev
@@ -936,6 +984,63 @@ class Vid2VidModelG(BaseModel):
         else:
             fp.win_u8[:, tG - 1].copy_(input_A[:, 0], non_blocking=True)
 
+    def _check_input_geometry(self, input_A):
+        """opt.input_geometry of a call that _check_inputs_u8 has let through: None with the option off, else (H, W,
+        geoms) -- the model-side size every stream's geometry yields and the int32 rows [new_w, new_h, x1, y1, flip, 0, 0, 0] of
+        the launch's table, one for a dict, B for a list.  Every refusal is raised here, before the call touches any state."""
+        from ..visual import geometry_words, GEOMETRY_MAX_SIZE
+        geometry = getattr(self.opt, "input_geometry", None)
+        if geometry is None:
+            return None
+        B, _, Hs, Ws, _ = input_A.shape
+        if not (1 <= Hs <= GEOMETRY_MAX_SIZE and 1 <= Ws <= GEOMETRY_MAX_SIZE):
+            raise ValueError("inference: opt.input_geometry takes source frames of 1..%d rows and columns, input_A has %dx%d"
+                             % (GEOMETRY_MAX_SIZE, Ws, Hs))
+        per_stream = isinstance(geometry, (list, tuple))
+        if per_stream and len(geometry) != B:
+            raise ValueError("inference: opt.input_geometry lists %d geometries for %d stream(s)" % (len(geometry), B))
+        words = [geometry_words(g) for g in (geometry if per_stream else [geometry])]
+        H, W = words[0][5:]
+        for b, w in enumerate(words):
+            if tuple(w[5:]) != (H, W):
+                raise ValueError("inference: opt.input_geometry gives stream %d frames of %dx%d, stream 0 of %dx%d: one plan runs "
+                                 "one size" % (b, w[6], w[5], W, H))
+        running = getattr(self, "fake_B_prev", None) is not None and self._active_plan is not None
+        if running and (self._active_plan.H, self._active_plan.W) != (H, W):
+            raise ValueError("inference: opt.input_geometry gives frames of %dx%d, the running sequences are at %dx%d; assign "
+                             "fake_B_prev = None to restart" % (W, H, self._active_plan.W, self._active_plan.H))
+        return H, W, [list(w[:5]) + [0, 0, 0] for w in words]
+
+    def _stage_inputs_geometry(self, fp, input_A, lut, rows, new, geo):
+        """uint8 inputs at source size (opt.input_geometry): ONE launch (Engine.gather_frames_u8) resizes, crops and
+        flips every frame the call brings into fp.win_u8 -- the plan's own windows or the pool's, stream b's window being
+        win_u8[b].  The streams in `new` send their whole window, every other stream of `rows` (the active ones, ascending) its
+        newest frame into slot tG - 1 of the window the plan has moved on; the idle streams' rows are not read.  Frames on the
+        host cross first, and only those the launch reads."""
+        from ..visual import gather_entries
+        tG, dev = self.opt.n_frames_G, self.device
+        if fp._lut_src is not lut:
+            fp.lut.copy_(lut)
+            fp._lut_src = lut
+        B, t_in = input_A.shape[:2]
+        entries = gather_entries(t_in, tG, rows, new, len(geo[2]) > 1)
+        if not entries:
+            return
+        if input_A.device != dev:
+            src = torch.empty(input_A.shape, dtype=torch.uint8, device=dev)
+            if len(rows) == B and (len(new) == B or t_in == 1):
+                src.copy_(input_A, non_blocking=True)
+            else:
+                for b in rows:
+                    if b in new:
+                        src[b].copy_(input_A[b], non_blocking=True)
+                    else:
+                        src[b, -1].copy_(input_A[b, -1], non_blocking=True)
+        else:
+            src = input_A.contiguous()
+        tables = fp.gather_tables(entries, geo[2])
+        self.engine.gather_frames_u8(src, fp.win_u8, *tables)
+
     def _seed_windows(self, windows, input_A, input_B, inst_A, new=None, lut=None):
         """Seed `windows` (a list per scale) from generate_first_frame: whole (new=None: the first frame of every sequence), or
         the streams in the list `new` alone, from their rows of the inputs alone (windows then have a leading stream dimension).
@@ -966,18 +1071,22 @@ class Vid2VidModelG(BaseModel):
             if fp.win_u8 is not None and self._active_plan.win_u8 is not None:      # the uint8 input window, as far as it has moved
                 fp.win_u8.copy_(self._active_plan.win_u8)
 
-    def _inference_slots(self, input_A, input_B, inst_A, act, rst, has_inst, u8, img=False, pic=False, lut=None):
+    def _inference_slots(self, input_A, input_B, inst_A, act, rst, has_inst, u8, img=False, pic=False, lut=None, geo=None):
         """One replay of the slot plan (B > 1).  act / rst: B bools.  On the first frame of the model
         (fake_B_prev = None) every active stream starts a sequence and the windows of the idle ones are zero.
         img (opt.frames_u8): the uint8 images the plan's last launch wrote, idle rows zero, instead of fake_B.
         pic (opt.real_A_u8): the uint8 input pictures the plan wrote, idle rows zero, instead of real_A_last.
-        lut (opt.inputs_u8 with opt.inputs_u8_slots): input_A is uint8 (B,t,H,W,in_ch) and this is the call's table."""
+        lut (opt.inputs_u8 with opt.inputs_u8_slots): input_A is uint8 (B,t,H,W,in_ch) and this is the call's table.
+        geo (opt.input_geometry): _check_input_geometry's result; input_A is at source size and one gather launch
+        stages it -- ahead of the first-frame generators, which then read a restarted stream's window at model size."""
         opt = self.opt
         in_u8 = lut is not None
         if in_u8:
             B, _, H, W, in_ch = input_A.shape
         else:
             B, _, in_ch, H, W = input_A.shape
+        if geo is not None:
+            H, W = geo[:2]
         fp = self._frame_plan(H, W, in_ch, has_inst, False, u8, B, slots=True, frames_u8=img, inputs_u8=in_u8, real_A_u8=pic,
                               inputs_u8_slots=in_u8)
         if self.is_first_frame:
@@ -994,9 +1103,13 @@ class Vid2VidModelG(BaseModel):
                 fp.win_u8.zero_()
         else:
             self._carry_windows(fp)                                              # plain plan -> slot plan
-        self._seed_windows(fp.prev, input_A, input_B, inst_A, new, lut)
-        if in_u8:                        # behind the carry: into the windows the sequences have reached
-            self._stage_inputs_u8_slots(fp, input_A, lut, rows, new)
+        if geo is not None:              # behind the carry, ahead of the seeding, which reads the gathered windows
+            self._stage_inputs_geometry(fp, input_A, lut, rows, new, geo)
+            self._seed_windows(fp.prev, fp.win_u8, input_B, inst_A, new, lut)
+        else:
+            self._seed_windows(fp.prev, input_A, input_B, inst_A, new, lut)
+            if in_u8:                    # behind the carry: into the windows the sequences have reached
+                self._stage_inputs_u8_slots(fp, input_A, lut, rows, new)
         fp.set_words([2 if not act[b] else (1 if (rst[b] and opt.no_first_img) else 0) for b in range(B)])
         self._active_plan = fp
         self.fake_B_prev = fp.prev
@@ -1009,20 +1122,24 @@ class Vid2VidModelG(BaseModel):
             fake[[b for b in range(B) if not act[b]]] = 0
         return fake, real_A
 
-    def _inference_pool(self, input_A, input_B, inst_A, act, rst, has_inst, u8, img=False, pic=False, lut=None):
+    def _inference_pool(self, input_A, input_B, inst_A, act, rst, has_inst, u8, img=False, pic=False, lut=None, geo=None):
         """One call of a compacting model (opt.compact_streams, B = S > 1 slots): the contract of _inference_slots,
         by a replay of the pool plan that has one row per ACTIVE stream -- row k runs slot rows[k], rows ascending.
         img (opt.frames_u8): the plan's last launch delivers the (S,H,W,3) uint8 images, idle slots zero; no zero tensor and no
         indexed copy for the frames.
         pic (opt.real_A_u8): the same for the second result, the (S,H,W,3) uint8 input pictures.
         lut (opt.inputs_u8 with opt.inputs_u8_slots): input_A is uint8 (S,t,H,W,in_ch), staged into the pool's uint8
-        input windows, slot b's rows into window b; the plan's rows reach them through row_slot."""
+        input windows, slot b's rows into window b; the plan's rows reach them through row_slot.
+        geo (opt.input_geometry): _check_input_geometry's result; input_A is at source size and one gather launch
+        writes slot b's frames into window b."""
         opt, dev = self.opt, self.device
         in_u8 = lut is not None
         if in_u8:
             S, _, H, W, in_ch = input_A.shape
         else:
             S, _, in_ch, H, W = input_A.shape
+        if geo is not None:
+            H, W = geo[:2]
         rows = [b for b in range(S) if act[b]]
         K = len(rows)
         last_C = in_ch if opt.label_nc == 0 else opt.label_nc + int(has_inst)
@@ -1049,11 +1166,13 @@ class Vid2VidModelG(BaseModel):
             if in_u8:
                 fp.win_u8.zero_()
         new = [b for b in range(S) if rst[b]]
-        if in_u8:
+        if geo is not None:
+            self._stage_inputs_geometry(fp, input_A, lut, rows, new, geo)  # the active streams' frames, resized into their windows
+        elif in_u8:
             self._stage_inputs_u8_slots(fp, input_A, lut, rows, new)      # the active streams' rows, each into its slot's window
         else:
             self._stage_inputs(fp, input_A, inst_A, has_inst, rows)       # the active streams' rows, straight into the dense rows
-        self._seed_windows(pool.windows, input_A, input_B, inst_A, new, lut)
+        self._seed_windows(pool.windows, fp.win_u8 if geo is not None else input_A, input_B, inst_A, new, lut)
         fp.set_words(rows + [1 if (rst[b] and opt.no_first_img) else 0 for b in rows])
         pool.idle = [b for b in range(S) if not act[b]]
         self._active_plan = fp

@@ -40,6 +40,10 @@ _DEFAULTS = dict(
     real_A_u8=False,          # inference's second result is the uint8 input picture (B,H,W,3) -- visual.tensor2label of real_A_last, written
                               # by one launch of the frame plan from the label map itself; tensor2im(normalize=False) of its first
                               # plane(s) for label_nc == 0 -- instead of the fp32 planes; read per call
+    input_geometry=None,      # with inputs_u8: input_A is uint8 (B,t,Hs,Ws,in_ch) at SOURCE size, and this is the reference's
+                              # get_img_params dict (new_size, crop_size, crop_pos, flip), or a list of B of them: one launch in front
+                              # of the frame plan does the loader's nearest resize, crop and flip into the plan's uint8 windows
+                              # (DESIGN 3.24); None: input_A is at model size, as before; read per call
     input_lut=None,           # fp32 (in_ch, 256): decoded value of every byte per channel; None = visual.input_lut(in_ch)
     ema_decay=0.0,           # training: > 0 keeps an exponential moving average of the generator's weights inside the Adam step
                               # and saves it as '<label>_net_G<s>_ema.pth' (DESIGN 3.17); 0 = off, nothing changes

@@ -12,6 +12,7 @@ does not stall a generator that runs at hundreds of frames per second.
     to_numpy(img)                 -> what the reference's function returns (numpy uint8)
 """
 import ctypes as C
+import operator
 import queue
 import threading
 
@@ -116,6 +117,104 @@ def decode_inputs(input_u8, lut):
     planes = input_u8.movedim(-1, -3).long()                                 # (..., C, H, W)
     idx = planes + (torch.arange(C_, device=input_u8.device) * 256).view(C_, 1, 1)
     return lut.reshape(-1)[idx]
+
+
+GEOMETRY_MAX_SIZE = 16384      # of a source frame and of new_size: keeps (2 xr + 1) Ws inside int32 (include/v2v_hip.h)
+
+
+def _int_pair(value, what):
+    try:
+        a, b = value
+        return operator.index(a), operator.index(b)
+    except (TypeError, ValueError):
+        raise ValueError("input geometry: %s is a pair of integers, got %r" % (what, value)) from None
+
+
+def geometry_words(geometry):
+    """(new_w, new_h, x1, y1, flip, H, W) of one geometry: the reference's get_img_params dict (data/base_dataset.py:85-128) --
+    new_size=(new_w, new_h); crop_size=(cw, ch), (0, 0) or missing for no crop stage; crop_pos=(x1, y1); flip=bool -- as
+    get_transform applies it with method=Image.NEAREST (:130-175): resize to new_size, then __crop (only if the resized frame
+    is wider or higher than crop_size, with the box clipped to the frame), then FLIP_LEFT_RIGHT.  x1, y1 are 0 where nothing
+    is cropped (crop_pos is then not looked at, as in the reference); (H, W) is the size of the result.  ValueError for
+    anything else."""
+    if not isinstance(geometry, dict):
+        raise ValueError("input geometry: a dict with the keys of get_img_params (new_size, crop_size, crop_pos, flip), got %r"
+                         % type(geometry).__name__)
+    unknown = set(geometry) - {"new_size", "crop_size", "crop_pos", "flip"}
+    if unknown or "new_size" not in geometry:
+        raise ValueError("input geometry: keys new_size (required), crop_size, crop_pos, flip; got %s" % sorted(geometry))
+    new_w, new_h = _int_pair(geometry["new_size"], "new_size")
+    if not (1 <= new_w <= GEOMETRY_MAX_SIZE and 1 <= new_h <= GEOMETRY_MAX_SIZE):
+        raise ValueError("input geometry: new_size within 1..%d, got %r" % (GEOMETRY_MAX_SIZE, (new_w, new_h)))
+    flip = geometry.get("flip", False)
+    if not isinstance(flip, (bool, np.bool_)):
+        raise ValueError("input geometry: flip is a bool, got %r" % (flip,))
+    cw, ch = _int_pair(geometry.get("crop_size", (0, 0)), "crop_size")
+    if cw < 0 or ch < 0:
+        raise ValueError("input geometry: crop_size is not negative, got %r" % ((cw, ch),))
+    x1 = y1 = 0
+    W, H = new_w, new_h
+    if (cw, ch) != (0, 0):                                             # a crop stage: its corner is checked even where
+        px, py = _int_pair(geometry.get("crop_pos", (0, 0)), "crop_pos")    # __crop then keeps the whole frame
+        if not (0 <= px < new_w and 0 <= py < new_h):
+            raise ValueError("input geometry: crop_pos %r is outside the resized %dx%d frame" % ((px, py), new_w, new_h))
+        if new_w > cw or new_h > ch:                                   # __crop: if (ow > tw or oh > th)
+            x1, y1 = px, py
+            W, H = min(new_w, x1 + cw) - x1, min(new_h, y1 + ch) - y1
+            if W < 1 or H < 1:
+                raise ValueError("input geometry: crop_size %r leaves an empty frame" % ((cw, ch),))
+    return new_w, new_h, x1, y1, int(bool(flip)), H, W
+
+
+def geometry_size(geometry):
+    """(H, W) of the frame that a geometry (geometry_words) yields: the size of the model's inputs under opt.input_geometry."""
+    return geometry_words(geometry)[5:]
+
+
+def gather_entries(t_in, tG, rows, new, per_stream):
+    """The entry table of one inference call under opt.input_geometry: input_A is (B, t_in, ...) viewed as B t_in
+    source frames, the uint8 windows (B or S, tG, ...) viewed as frames.  A stream of `new` (started or restarted) sends all its
+    t_in == tG frames to its window's slots; every other stream of `rows` (the active ones) sends its newest frame to slot
+    tG - 1; streams outside `rows` get no entry.  [src_frame, dst_frame, geom, 0] per entry, geom = the stream with a geometry
+    per stream, else 0."""
+    entries = []
+    for b in rows:
+        g = b if per_stream else 0
+        if b in new:
+            if t_in != tG:
+                raise ValueError("a started stream brings its whole window (t = %d), got t = %d" % (tG, t_in))
+            entries += [[b * t_in + t, b * tG + t, g, 0] for t in range(tG)]
+        else:
+            entries.append([b * t_in + t_in - 1, b * tG + tG - 1, g, 0])
+    return entries
+
+
+def resample_u8(src, geometry, out=None):
+    """uint8 frames (F, Hs, Ws, C) -> (F, H, W, C) under one geometry (geometry_words), by v2v_gather_frames_u8 on its own: the
+    reference loader's img.resize(new_size, Image.NEAREST), __crop and flip of every frame, byte for byte.  The bytes may be
+    anything -- image channels or label / instance ids (the loaders resize label maps with NEAREST too).  out: a contiguous
+    uint8 device tensor (F, H, W, C) to write into."""
+    if not isinstance(src, torch.Tensor) or src.dtype != torch.uint8 or src.dim() != 4:
+        raise ValueError("resample_u8: uint8 frames (F, Hs, Ws, C)")
+    words = geometry_words(geometry)
+    F, Hs, Ws, Cc = src.shape
+    H, W = words[5:]
+    if not (1 <= Hs <= GEOMETRY_MAX_SIZE and 1 <= Ws <= GEOMETRY_MAX_SIZE and 1 <= Cc <= 32 and F >= 1):
+        raise ValueError("resample_u8: frames of 1..%d rows and columns and 1..32 channels, got %s" % (GEOMETRY_MAX_SIZE, tuple(src.shape)))
+    if not src.is_cuda and not lib.v2v_get_dry_run():
+        raise ValueError("resample_u8: the frames are in device memory")
+    src = src.contiguous()
+    if out is None:
+        out = torch.empty((F, H, W, Cc), dtype=torch.uint8, device=src.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (F, H, W, Cc)
+          or not out.is_contiguous() or out.device != src.device):
+        raise ValueError("resample_u8: out is contiguous uint8 %s on the frames' device" % ((F, H, W, Cc),))
+    # entries [F][4] then the geometry [8], one int32 buffer (both tables 16-byte aligned)
+    table = torch.tensor([w for f in range(F) for w in (f, f, 0, 0)] + list(words[:5]) + [0, 0, 0], dtype=torch.int32).to(src.device)
+    check(lib.v2v_gather_frames_u8(C.c_void_p(src.data_ptr()), F, Hs, Ws, C.c_void_p(out.data_ptr()), F, H, W, Cc,
+                                   C.c_void_p(table.data_ptr()), F, C.c_void_p(table.data_ptr() + 16 * F), 1, _stream(src)),
+          "gather_frames_u8")
+    return out
 
 
 def tensor2label(output, n_label):
